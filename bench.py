@@ -7,7 +7,12 @@ the interpreter over all rows, reduce, copy losses back, exact re-check when nee
 full cost of one `eval_cost_batch` call of a search iteration).  Trees and data are synthetic
 (seeded), generated before timing; the dataset is resident in HBM when the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set up, W warm-up steps, K timed steps, the
+outputs of the last timed step into DIR (--dump-outputs: loss.npy, loss_nonfinite.npy and complete.npy, float32, all finite), one
+JSON line.  --full adds every other measurement and check described below (the sub-objects, the
+CPU baseline, the parities, the searches), each a run of its own after the headline.
 
 --gpus N without a launcher (WORLD_SIZE unset) starts N rank processes itself (fresh children of a
 parent that makes no GPU call; rank 0 prints).  Under torch.distributed.run the launcher's ranks are
@@ -19,10 +24,10 @@ Headline, C2 (BASELINE config 2): 10k trees x 1M rows x 5 features PER GPU, weak
   dataset, and the step is the row-sharded call (sr_eval_loss_sharded: ONE RCCL all-reduce of packed
   per-tree partials).  `c2_sharded_path` (N = 1) times the same step through the row-sharded call at
   world size 1, so the scaling denominator's code path is on record.
-Sub-objects measured at every N, each through the same code path at every N:
+Sub-objects measured at every N with --full, each through the same code path at every N:
   c4            BASELINE config 4: 100k trees x 64M (2^26) rows, rows sharded n/N (strong scaling).
   tree_sharded  the C2 population over a replicated 1M-row dataset, trees dealt over the N ranks.
-Rank 0 at N = 1 also reports: the interpreter roofline, the complete-trees-only and Float64 lines,
+Rank 0 at N = 1 with --full also reports: the fold's cost, the complete-trees-only and Float64 lines,
 the CPU baseline (the C oracle on the host cores) and the parity of the timed step against it, and
 the search throughput (C1 and C3) with the same engine scored by the C port as its CPU baseline.
 """
@@ -52,6 +57,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (fold cost, sharded paths, C4, "
+                         "complete-only and Float64 lines, CPU baseline and parity, searches); the --no-* options, "
+                         "--c4-*, --cpu-trees and --search-* select among those legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss.npy, loss_nonfinite.npy, complete.npy; "
+                         "float32, every entry finite) into DIR")
     ap.add_argument("--rows", type=int, default=0, help="C2 rows per GPU (default 2^20)")
     ap.add_argument("--trees", type=int, default=0, help="C2 trees (default 10k)")
     ap.add_argument("--c4-rows", type=int, default=1 << 26, help="C4 total rows (multiple of 2^20 x N)")
@@ -70,7 +82,10 @@ def parse_args(argv=None):
                     help="launcher + CPU channel only (no device): rehearses --gpus N on a CPU host")
     ap.add_argument("--search-cpu-iters", type=int, default=0,
                     help="iterations of the CPU-port searches (0 = C1: all, C3: 2, a bounded sample)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -152,6 +167,22 @@ class Comm:
         self.d.destroy_process_group()
 
 
+class SoloComm:
+    """A plain one-GPU run's CPU channel: one process, nothing to exchange (no process group; torch is
+    not imported)."""
+
+    world, rank = 1, 0
+
+    def barrier(self):
+        pass
+
+    def max(self, v):
+        return float(v)
+
+    def close(self):
+        pass
+
+
 def progress(msg):
     """A progress line on stderr (long runs: the bench's phases each print one as they start)."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -202,6 +233,21 @@ def single_gpu_call(ctx, tb, ds, opts, dtype=np.float32):
     return call, out
 
 
+def dump_outputs(d, loss, comp):
+    """--dump-outputs: what the last timed step's call returned to its caller, one array per file, all
+    trees, float32, every entry finite so that the files compare with plain arithmetic: loss.npy holds
+    the per-tree losses, 0 where a loss is not finite (an incomplete tree scores +Inf; a complete tree's
+    fold may overflow); loss_nonfinite.npy says which those are (0 finite, 1 +Inf, 2 -Inf, 3 NaN);
+    complete.npy holds the complete flags as 0 / 1.  Trees and data are seeded, so two builds run with
+    the same arguments can be compared file for file."""
+    os.makedirs(d, exist_ok=True)
+    loss = np.asarray(loss, dtype=np.float32)
+    kind = np.where(np.isnan(loss), 3, np.where(np.isposinf(loss), 1, np.where(np.isneginf(loss), 2, 0)))
+    np.save(os.path.join(d, "loss.npy"), np.where(kind == 0, loss, np.float32(0)).astype(np.float32))
+    np.save(os.path.join(d, "loss_nonfinite.npy"), kind.astype(np.float32))
+    np.save(os.path.join(d, "complete.npy"), np.asarray(comp, dtype=np.float32))
+
+
 def roofline(flops, kernel_ms, peak, **extra):
     achieved = flops / (kernel_ms * 1e-3) / 1e12
     out = {"bound": "valu", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
@@ -233,7 +279,9 @@ def main():
     from sr_amd import Dataset, Options, flatten_trees, gen_random_batch, gen_random_population
     from sr_amd.distributed import comm_info, eval_loss_sharded, eval_loss_tree_sharded, init_device_comm
 
-    comm = Comm(world, rank)
+    # a plain one-GPU run times the single-GPU call alone: no process group and no communicator
+    solo = world == 1 and not args.full
+    comm = SoloComm() if solo else Comm(world, rank)
     # the device: LOCAL_RANK, or SR_AMD_DEVICE (a rehearsal on a one-GPU box puts every rank on device 0;
     # RCCL refuses two ranks on one device, so that run takes the gloo exchange below)
     ctx = sr_amd.get_context(int(os.environ.get("SR_AMD_DEVICE", local_rank)))
@@ -243,7 +291,8 @@ def main():
     # printing nothing
     err = None
     try:
-        init_device_comm(ctx=ctx)
+        if not solo:
+            init_device_comm(ctx=ctx)
     except Exception as e:  # noqa: BLE001  (reported in the JSON line)
         if world == 1:
             raise
@@ -257,6 +306,9 @@ def main():
         from sr_amd.distributed import init_host_comm
         init_host_comm(ctx=ctx)
         cinfo = {"nranks": None, "rccl_error": err or "failed on a peer rank", "transport": "host (gloo)"}
+    elif solo:
+        from sr_amd._lib import runtime_info
+        cinfo = dict(runtime_info(), nranks=None)
     else:
         cinfo = comm_info(ctx)
 
@@ -298,9 +350,13 @@ def main():
     n_derived = ctx.last_derived_columns()
     n_exact_last, n_fold_last = ctx.last_exact_trees(), ctx.last_fold_trees()
     ref_fold = ctx.last_ref_fold()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, comp)
 
+    # everything below the headline (--full): each leg is a run of its own
+    full = args.full
     subs = {}
-    if world == 1:  # the fold's cost on the headline step: the same step with the f64 sums
+    if full and world == 1:  # the fold's cost on the headline step: the same step with the f64 sums
         ctx.set_tuning("ref_fold", 0)
         call0, _ = single_gpu_call(ctx, tb, ds, opts)
         st0 = {}
@@ -312,30 +368,30 @@ def main():
             "trees_fallback": ref_fold["fallback"], "path": ref_fold["path"],
             "note": ("ref_fold 1 (default): every complete tree's loss is the reference's in-order Float32 fold; "
                      "ref_fold 0: the f64 per-tree sums of rounds 1-5 (~5e-4 relative off at 2^20 rows)")}
-    if world == 1 and not args.no_sharded_path:
+    if full and world == 1 and not args.no_sharded_path:
         if rank == 0:
             progress("c2_sharded_path")
         subs["c2_sharded_path"] = sharded_path_line(ctx, tb, ds, opts, eval_loss_sharded, args, comm, nodes, rows)
-    if not args.no_tree_sharded:
+    if full and not args.no_tree_sharded:
         if rank == 0:
             progress("tree_sharded")
         subs["tree_sharded"] = tree_sharded_line(ctx, tb, opts, eval_loss_tree_sharded, args, comm, world, rank,
                                                  nodes, rows, loss if world == 1 else None, comp if world == 1 else None)
-    if not args.no_c4:
+    if full and not args.no_c4:
         if rank == 0:
             progress("c4")
         subs["c4"] = c4_line(ctx, opts, eval_loss_sharded, gen_random_batch, Dataset, args, comm, world, rank)
 
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra:
+    if full and rank == 0 and world == 1 and not args.no_extra:
         progress("complete-only and Float64 lines")
         extra = extra_lines(ctx, opts, trees, comp, X, y, args)
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("CPU baseline and parity")
         cpu, parity = cpu_baseline_and_parity(opts, tb, X, y, args.cpu_trees, loss, comp)
     search = None
-    if rank == 0 and world == 1 and args.search_iters > 0:
+    if full and rank == 0 and world == 1 and args.search_iters > 0:
         search = search_lines(args)
 
     if rank == 0:
@@ -350,6 +406,7 @@ def main():
             **({"rccl_error": cinfo["rccl_error"], "transport": cinfo["transport"]} if cinfo.get("rccl_error") else {}),
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": dt / args.steps * 1e3,
             "step_ms_min_median_max": [float(step_ms.min()), float(np.median(step_ms)), float(step_ms.max())],
             "higher_is_better": True,

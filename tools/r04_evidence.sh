@@ -8,8 +8,8 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=${1:-gpurun_out/r04_evidence}
 rm -rf $OUT; mkdir -p $OUT/c2 $OUT/c4 $OUT/grad
-C2="--no-cpu-baseline --search-iters 0 --no-extra --no-c4 --no-tree-sharded --no-sharded-path"
-C4="--no-cpu-baseline --search-iters 0 --no-extra --no-tree-sharded --no-sharded-path --no-c4-parity --steps 3 --warmup 2 --c4-steps 3"
+C2="--full --no-cpu-baseline --search-iters 0 --no-extra --no-c4 --no-tree-sharded --no-sharded-path"
+C4="--full --no-cpu-baseline --search-iters 0 --no-extra --no-tree-sharded --no-sharded-path --no-c4-parity --steps 3 --warmup 2 --c4-steps 3"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c2/kt -o kt -- \
   python3 bench.py $C2 > $OUT/c2/bench_traced.json 2> $OUT/c2/kt.err || exit $?
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/c2/pmc -o pmc -- \

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 TAG=$1; shift
 OUT=gpurun_out/$TAG
 rm -rf $OUT; mkdir -p $OUT
-C2="--no-cpu-baseline --search-iters 0 --no-extra --no-c4 --no-tree-sharded --no-sharded-path"
+C2="--full --no-cpu-baseline --search-iters 0 --no-extra --no-c4 --no-tree-sharded --no-sharded-path"
 SR_AMD_FOLD_STATS=1 timeout -k 10 200 python3 bench.py --steps 2 --warmup 1 $C2 > $OUT/stats.json 2> $OUT/stats.err || exit $?
 i=0
 for v in "$@"; do

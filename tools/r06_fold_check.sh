@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 TAG=${1:-r06x}
 OUT=gpurun_out/${TAG}
 rm -rf $OUT; mkdir -p $OUT
-C2="--no-cpu-baseline --search-iters 0 --no-extra --no-c4 --no-tree-sharded --no-sharded-path"
+C2="--full --no-cpu-baseline --search-iters 0 --no-extra --no-c4 --no-tree-sharded --no-sharded-path"
 if [ "$PYTEST_K" != "none" ]; then
   timeout -k 10 400 python3 -u -m pytest tests/test_gpu_ref_fold.py -x -v --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > $OUT/fold.log 2>&1 || exit $?
 fi
