@@ -86,6 +86,26 @@ typedef struct sr_tree_batch {
   const void* val;          /* Node.val (leaf, constant): Float32 or Float64 = dataset dtype */
 } sr_tree_batch;
 
+/*
+ * The parameter side of a batch of ParametricExpression trees (src/ParametricExpression.jl:69-100;
+ * DynamicExpressions' ParametricNode fields), parallel to a sr_tree_batch: node i of the tree batch is the
+ * parameter leaf p<parameter[i]> when is_parameter[i] != 0 (a leaf with constant == 0; its `feature` is
+ * ignored), and tree t reads parameters_t[k, class[row]] from its own (max_parameters, n_classes) matrix:
+ * `parameters` holds the n_trees matrices one after another, each in Julia's column-major layout (address
+ * k + max_parameters * c, both 0-based), in the dataset's element type.  A parameter leaf is evaluated as
+ * the feature leaf nfeatures + k of [X; parameters[:, class]] (DynamicExpressions' eval_tree_array for
+ * ParametricExpression): the same fused kernels, checks and loss fold as a plain feature leaf; it is never
+ * constant-folded.  Gradients, constant optimisation, the sharded calls and the native search take plain
+ * trees only.
+ */
+typedef struct sr_param_batch {
+  const uint8_t* is_parameter; /* per node: ParametricNode.is_parameter */
+  const uint16_t* parameter;   /* per node: ParametricNode.parameter, 1-based (where is_parameter) */
+  int32_t max_parameters;      /* rows of every parameter matrix (<= 65535) */
+  int32_t n_classes;           /* columns of every parameter matrix = the dataset's n_classes */
+  const void* parameters;      /* [n_trees][n_classes][max_parameters] as laid out above */
+} sr_param_batch;
+
 /* ------------------------------------------------------------------ library / device */
 const char* sr_last_error(void);
 int sr_version(void);
@@ -117,6 +137,15 @@ int sr_register_loss(sr_ctx* ctx, int kind, double param, int* loss_code);
  */
 int sr_dataset_upload(sr_ctx* ctx, int dtype, const void* X, int64_t nfeatures, int64_t n,
                       const void* y, const void* weights, sr_dataset** out);
+/*
+ * The same with the per-row class column of a parametric search (dataset.extra.class): cls[n], Julia's
+ * 1-based ids in 1..n_classes (SR_ERR_INVALID_ARG otherwise; n_classes < 2^24).  The device keeps the class
+ * as one hidden extra row of X; sr_dataset_info still reports the user's nfeatures, and every plain call
+ * on such a dataset returns exactly what it returns on the dataset uploaded without classes.
+ */
+int sr_dataset_upload_classes(sr_ctx* ctx, int dtype, const void* X, int64_t nfeatures, int64_t n,
+                              const void* y, const void* weights, const int32_t* cls, int32_t n_classes,
+                              sr_dataset** out);
 int sr_dataset_free(sr_dataset* ds);
 int sr_dataset_info(const sr_dataset* ds, int* dtype, int64_t* nfeatures, int64_t* n);
 
@@ -148,6 +177,30 @@ int sr_eval_loss_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, co
  */
 int sr_eval_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                        const int64_t* row_idx, int64_t n_idx, void* out_pred, uint8_t* out_complete);
+
+/*
+ * The three calls above for ParametricExpression trees (eval_tree_dispatch(::ParametricExpression, ...),
+ * src/ParametricExpression.jl:69-100): the plain call's arguments plus the batch's parameter side, the
+ * same outputs.  `ds` must come from sr_dataset_upload_classes with params->n_classes classes
+ * (SR_ERR_INVALID_ARG otherwise); SR_ERR_BAD_TREE for a parameter index of 0 or above max_parameters, for
+ * is_parameter on an operator node and for is_parameter together with constant.  A tree is scored on its
+ * own matrix: results do not depend on the other trees of the batch.  The deferred validity checks bound
+ * leaf values by max(max|X|, max|parameters|) over the call (Inf when an entry is non-finite, used by a row
+ * or not); such a call runs the per-node-check kernels.  Parametric calls run their own, smaller set of
+ * kernel builds (csrc/sr_inst_*param*.hip): of the tuning knobs, "rows_per_lane" only chooses between the
+ * classic build and the one register-stack build per type, the 8-wave build and derived columns are not
+ * used; results do not depend on either.
+ */
+int sr_eval_loss_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx,
+                                  int loss_kind, void* out_loss, uint8_t* out_complete);
+int sr_eval_loss_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                        const sr_param_batch* params, const int32_t* tree_view, int n_views,
+                                        const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
+                                        uint8_t* out_complete);
+int sr_eval_tree_array_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx,
+                                  void* out_pred, uint8_t* out_complete);
 
 /*
  * Row-sharded form for multi-GPU scoring.  The dataset on this rank holds one shard of the
@@ -284,6 +337,15 @@ int sr_compile_info(int dtype, int n_unary, const char* const* unary_names, int 
                     const char* const* binary_names, const sr_tree_batch* trees, int64_t n_rows,
                     int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
                     void* out_code, int64_t code_capacity);
+/* The same for ParametricExpression trees (params->parameters and n_classes are not read: the programs
+ * depend on the node arrays and max_parameters alone).  Per tree, out_static_bad and the stack depth equal
+ * those of the tree with every parameter leaf p_k replaced by the feature leaf x_(nfeatures + k), compiled
+ * by sr_compile_info with nfeatures + max_parameters features. */
+int sr_compile_info_parametric(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                               const char* const* binary_names, const sr_tree_batch* trees,
+                               const sr_param_batch* params, int64_t n_rows, int64_t nfeatures, int32_t* out_len,
+                               uint8_t* out_static_bad, int32_t* out_max_depth, void* out_code,
+                               int64_t code_capacity);
 
 /*
  * Host-side evaluation of one unary operator (the code constant folding uses; the device runs the

@@ -1480,6 +1480,58 @@ hipError_t sr_launch_eval(const SrEvalArgs<T>& a, int mode, bool gather, int tie
 }
 template hipError_t sr_launch_eval<float>(const SrEvalArgs<float>&, int, bool, int, int, int, bool, int, hipStream_t);
 template hipError_t sr_launch_eval<double>(const SrEvalArgs<double>&, int, bool, int, int, int, bool, int, hipStream_t);
+
+// The kernels of parametric calls (sr_inst_*param*.hip): the L2 and generic-loss builds only (L1 runs
+// the generic one), 4 waves everywhere, FOLD with the generic loss, EXACT in its FULL-tier build.
+template <typename T, int R, bool VSTK>
+static hipError_t sr_launch_param_basic_loss(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int n_blocks, hipStream_t s) {
+  if (a.loss_kind == SR_LOSS_L2)
+    return sr_launch_tile_param<T, R, SR_MODE_LOSS, false, SR_TIER_BASIC, 4, SR_LOSS_L2, VSTK>(a, p, n_blocks, s);
+  return sr_launch_tile_param<T, R, SR_MODE_LOSS, false, SR_TIER_BASIC, 4, -1, VSTK>(a, p, n_blocks, s);
+}
+template <typename T>
+hipError_t sr_launch_eval_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int mode, bool gather, int tier, int R,
+                                int waves, bool vstk, int n_blocks, hipStream_t s) {
+  constexpr int RB = sizeof(T) == 4 ? 8 : 4;   // BASIC classic rows per lane
+  constexpr int RV = sizeof(T) == 4 ? 16 : 8;  // BASIC register-stack rows per lane
+  constexpr int RF = sizeof(T) == 4 ? 4 : 2;   // FULL tier / PRED / EXACT rows per lane
+  if (waves != 4) return hipErrorInvalidValue;
+  if (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC) {
+    if (vstk) return (R == RV && !gather) ? sr_launch_param_basic_loss<T, RV, true>(a, p, n_blocks, s) : hipErrorInvalidValue;
+    if (R != RB) return hipErrorInvalidValue;
+    if (gather) return sr_launch_tile_param<T, RB, SR_MODE_LOSS, true, SR_TIER_BASIC, 4, -1, false>(a, p, n_blocks, s);
+    return sr_launch_param_basic_loss<T, RB, false>(a, p, n_blocks, s);
+  }
+  if (mode == SR_MODE_FOLD) {
+    if constexpr (sizeof(T) == 4) {
+      if (tier == SR_TIER_BASIC) {
+        if (vstk)
+          return (R == RV && !gather) ? sr_launch_tile_param<T, RV, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, -1, true>(a, p, n_blocks, s)
+                                      : hipErrorInvalidValue;
+        if (R != RB) return hipErrorInvalidValue;
+        return gather ? sr_launch_tile_param<T, RB, SR_MODE_FOLD, true, SR_TIER_BASIC, 4, -1, false>(a, p, n_blocks, s)
+                      : sr_launch_tile_param<T, RB, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, -1, false>(a, p, n_blocks, s);
+      }
+      if (vstk || R != RF) return hipErrorInvalidValue;
+      return gather ? sr_launch_tile_param<T, RF, SR_MODE_FOLD, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
+                    : sr_launch_tile_param<T, RF, SR_MODE_FOLD, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
+    }
+    return hipErrorInvalidValue;  // (Float64: small calls only, from stored losses)
+  }
+  if (vstk || R != RF) return hipErrorInvalidValue;
+  if (mode == SR_MODE_LOSS)
+    return gather ? sr_launch_tile_param<T, RF, SR_MODE_LOSS, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
+                  : sr_launch_tile_param<T, RF, SR_MODE_LOSS, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
+  if (mode == SR_MODE_PRED)
+    return gather ? sr_launch_tile_param<T, RF, SR_MODE_PRED, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
+                  : sr_launch_tile_param<T, RF, SR_MODE_PRED, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
+  if (mode == SR_MODE_EXACT)
+    return gather ? sr_launch_tile_param<T, RF, SR_MODE_EXACT, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
+                  : sr_launch_tile_param<T, RF, SR_MODE_EXACT, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
+  return hipErrorInvalidValue;
+}
+template hipError_t sr_launch_eval_param<float>(const SrEvalArgs<float>&, const SrParamArgs<float>&, int, bool, int, int, int, bool, int, hipStream_t);
+template hipError_t sr_launch_eval_param<double>(const SrEvalArgs<double>&, const SrParamArgs<double>&, int, bool, int, int, int, bool, int, hipStream_t);
 template hipError_t sr_launch_transpose<float>(const float*, int64_t, int64_t, int64_t, float*, hipStream_t);
 template hipError_t sr_launch_transpose<double>(const double*, int64_t, int64_t, int64_t, double*, hipStream_t);
 template hipError_t sr_launch_pad<float>(float*, int64_t, int64_t, float, int, hipStream_t);

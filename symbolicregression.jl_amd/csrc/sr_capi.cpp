@@ -331,6 +331,13 @@ struct sr_ctx {
   bool fold_timed_last = false;
   int64_t n_ref_ok_last = 0, n_ref_fail_last = 0;  // trees whose loss is the walk's fold / that fell back
   double fold_kernel_ms_last = 0.0;
+  // A parametric call (sr_eval_*_parametric): the parameter side of the batch the running call scores,
+  // set by the entry point for the call's duration (under the context's lock); run_batch and the
+  // exact-sum pass then compile parameter leaves, upload the table and launch the PARAM kernels.  The
+  // fold's prediction passes over a few trees of the batch swap in those trees' side (fold_prepare).
+  const sr_param_batch* param = nullptr;
+  DevBuf ptab;     // the last parametric run_batch's table, [tree][parameter][class] (T)
+  HostBuf h_ptab;  // its pinned staging
 };
 
 // For the search engine (sr_search.cpp, not in the public header): set the context's "timing" knob
@@ -354,6 +361,9 @@ struct sr_dataset {
   double wsum = 0.0;
   double w_min = 0.0;      // smallest weight (the loss-fold overflow rule needs w >= 0: sr_fold.h)
   double max_abs_x = 0.0;  // max |X| over the data (NaN / Inf if any value is non-finite)
+  // sr_dataset_upload_classes: the rows' classes, 0-based in T, as row nf of X (a hidden extra row: nf,
+  // max_abs_x and the probe's stress rows leave it out; only parametric calls stage it); 0: no classes
+  int32_t n_classes = 0;
   mutable double wsum_jl_f32 = NAN, wsum_jl_f64 = NAN;  // Base.sum(w) in Float32 / Float64 (cached on first use)
   // dead-tree probe rows (large datasets): the "stress rows" — per feature the K largest, K smallest
   // and K smallest-magnitude values, where exp overflows, logs and divisions blow up — then rows 0, 1,
@@ -534,6 +544,7 @@ inline int64_t fold_terms(const sr_dataset* ds, int64_t n_rows) { return (ds->w 
 template <typename T>
 struct FoldRegion {
   SrEvalArgs<T> a;
+  SrParamArgs<T> p;  // (a parametric call's second argument block; ptab NULL otherwise)
   int64_t t0, pos0, np, n_blocks;
   int Rc;
   bool vstk;
@@ -607,7 +618,10 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
   fa.fold_loss = ctx->fold_store.as<T>();
   fa.fold_slot_rows = job.slot_rows;
   fa.fold_pos_stride = 0;
-  SR_HIP_CHECK(sr_launch_eval<T>(fa, SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, int(fr.n_blocks), cs));
+  if (fr.p.ptab)  // (a parametric call's launches: the PARAM builds)
+    SR_HIP_CHECK(sr_launch_eval_param<T>(fa, fr.p, SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, int(fr.n_blocks), cs));
+  else
+    SR_HIP_CHECK(sr_launch_eval<T>(fa, SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, int(fr.n_blocks), cs));
   return SR_OK;
 }
 // A region's walk: the folds' values and status at the caller's tree index (out arrays and carry are
@@ -677,26 +691,71 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
   // (SR_TRACK_LITE: the deferred-check kernels bound untracked values by L x max|x| for trees of up to
   //  L nodes; data at or above tbig / L — huge or non-finite values, never seen in practice — runs the
   //  per-node-check kernels instead, whose checks hold for any data)
+  // A parametric call (sr_ctx::param): the table the kernels gather from, [tree][parameter][class] in T
+  // (each tree's Julia column-major matrix transposed, so that one parameter's classes are contiguous),
+  // staged in pinned memory here and uploaded below; the leaf bound of the deferred checks becomes
+  // max(max|X|, max|P|), Inf when any entry is non-finite (then, as for such data, the per-node-check
+  // tier runs: DESIGN.md §4.6).  nfk: the X rows a launch stages (the hidden class row included).
+  const sr_param_batch* const pb = ctx->param;
+  const bool parametric = pb != nullptr;
+  const int nfk = int(ds->nf) + (parametric ? 1 : 0);
+  int64_t p_stride = 0;
+  double max_abs_p = 0.0;
+  if (parametric) {
+    if (shard) return set_error(SR_ERR_INVALID_ARG, "parametric trees are not supported by the sharded calls");
+    if (ds->n_classes <= 0) return set_error(SR_ERR_INVALID_ARG, "a parametric call needs a dataset uploaded with classes");
+    if (pb->n_classes != ds->n_classes)
+      return set_error(SR_ERR_INVALID_ARG, "sr_param_batch n_classes " + std::to_string(pb->n_classes) +
+                                               " differs from the dataset's " + std::to_string(ds->n_classes));
+    if (pb->max_parameters < 0 || pb->max_parameters > 65535) return set_error(SR_ERR_INVALID_ARG, "bad max_parameters");
+    if (nt > 0 && (!pb->is_parameter || !pb->parameter || (pb->max_parameters > 0 && !pb->parameters)))
+      return set_error(SR_ERR_INVALID_ARG, "sr_param_batch has NULL arrays");
+    const int64_t K = pb->max_parameters, NC = pb->n_classes;
+    p_stride = K * NC;
+    if (p_stride > int64_t(INT_MAX)) return set_error(SR_ERR_INVALID_ARG, "parameter matrix too large");
+    const size_t bytes = size_t(std::max<int64_t>(nt, 1)) * size_t(std::max<int64_t>(p_stride, 1)) * sizeof(T);
+    SR_HIP_CHECK(ctx->h_ptab.ensure(bytes, ctx->stream, ctx->stream2));
+    SR_HIP_CHECK(ctx->ptab.ensure(bytes));
+    T* hp = ctx->h_ptab.as<T>();
+    const T* src = static_cast<const T*>(pb->parameters);
+    bool bad = false;
+    for (int64_t t = 0; t < nt; ++t)
+      for (int64_t c = 0; c < NC; ++c)
+        for (int64_t k = 0; k < K; ++k) {
+          const T v = src[size_t(t) * size_t(p_stride) + size_t(c * K + k)];
+          hp[size_t(t) * size_t(p_stride) + size_t(k * NC + c)] = v;
+          const double m = std::fabs(double(v));
+          bad |= !std::isfinite(m);
+          max_abs_p = m > max_abs_p ? m : max_abs_p;
+        }
+    if (bad) max_abs_p = double(INFINITY);
+    allow_derived = false;  // (derived columns are chosen for plain populations: not measured here)
+  }
+  // the largest leaf value of the call, as the deferred checks bound it
+  auto leaf_bound = [&](double max_abs_x_data) { return parametric ? std::max(max_abs_x_data, max_abs_p) : max_abs_x_data; };
   int tier = ctx->tiers[opset_id];
 #ifdef SR_TRACK_LITE
   if (tier == SR_TIER_BASIC && mode == SR_MODE_LOSS && nt > 0) {
     int64_t lmax = 1;
     for (int64_t t = 0; t < nt; ++t) lmax = std::max<int64_t>(lmax, trees->offsets[t + 1] - trees->offsets[t]);
-    const double mx = shard ? shard->max_abs_x : ds->max_abs_x;
+    const double mx = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
     if (!(mx < double(T(t_max<T>() / (2.0 * double(n_total > 0 ? n_total : 1)))) / double(lmax))) tier = SR_TIER_FULL;
   }
 #endif
-  const int R = sr_rows_per_lane<T>(mode, tier, ctx->rows_override);
-  const int W = sr_waves_per_block(int(sizeof(T)), mode, tier, R, ctx->waves_override);
+  // (a parametric call's kernels are a smaller set, sr_launch_eval_param: the classic kernel at its
+  //  default rows per lane, 4 waves, one register-stack build per type; its knobs map onto that set)
+  const int R = sr_rows_per_lane<T>(mode, tier, parametric ? 0 : ctx->rows_override);
+  const int W = parametric ? 4 : sr_waves_per_block(int(sizeof(T)), mode, tier, R, ctx->waves_override);
   // register-stack kernel (f32 BASIC loss over the full dataset): Rv rows per lane, used for every
   // chunk whose programs need <= 2 operand-stack slots (all trees of <= 30 nodes); other chunks run
   // the LDS-stack kernel at R rows per lane
   int Rv = (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && !gather)
                ? sr_vstk_rows(int(sizeof(T)), n_eval, ctx->vstk_rows ? ctx->vstk_rows : ctx->rows_override)
                : 0;
+  if (parametric && Rv > 0) Rv = sizeof(T) == 4 ? 16 : 8;  // (the one register-stack build of a parametric call)
   // a wide dataset whose register-stack tile (its rows per lane are twice the classic kernel's) would
   // not fit the LDS runs the classic kernel instead (Float64 with ~40-75 features)
-  if (Rv > 0 && make_grid<T>(n_eval, nt > 0 ? nt : 1, Rv, W, int(ds->nf), 0, 0, ds->w != nullptr, ctx->tree_group,
+  if (Rv > 0 && make_grid<T>(n_eval, nt > 0 ? nt : 1, Rv, W, nfk, 0, 0, ds->w != nullptr, ctx->tree_group,
                              mrb).lds > kLdsMax)
     Rv = 0;
   ctx->rows_last = Rv > 0 ? Rv : R;  // (every C2-like tree fits the register stack)
@@ -725,11 +784,11 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
 
   // device + pinned buffers sized for the whole batch up front (a chunk's kernel may still run while
   // the next one is staged): a program has at most one instruction per node
-  Grid g0 = make_grid<T>(n_eval, nt > 0 ? nt : 1, R, W, int(ds->nf), 1, 0, ds->w != nullptr, ctx->tree_group,
+  Grid g0 = make_grid<T>(n_eval, nt > 0 ? nt : 1, R, W, nfk, 1, 0, ds->w != nullptr, ctx->tree_group,
                          mrb);
   int n_rb = g0.n_row_blocks;  // row blocks the partial buffers hold per tree (the most any kernel uses)
   if (Rv > 0)
-    n_rb = std::max(n_rb, make_grid<T>(n_eval, nt > 0 ? nt : 1, Rv, W, int(ds->nf), 0, 0, ds->w != nullptr,
+    n_rb = std::max(n_rb, make_grid<T>(n_eval, nt > 0 ? nt : 1, Rv, W, nfk, 0, 0, ds->w != nullptr,
                                        ctx->tree_group, mrb).n_row_blocks);
   const size_t code_cap = size_t(total_nodes) + 16;
   auto align256 = [](size_t x) { return (x + 255) & ~size_t(255); };
@@ -767,7 +826,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
   if (ctx->want_fold && ctx->ref_fold && mode == SR_MODE_LOSS && nt > 0 && fold_n_terms > 0) {
     // rows a position's store covers under either kernel's grid (row blocks x rows: >= the view)
     auto cover = [&](int Rc, int depth_c, int64_t* rb_rows) {
-      const Grid gg = make_grid<T>(n_eval, nt, Rc, W, int(ds->nf), depth_c, 0, ds->w != nullptr, ctx->tree_group, mrb);
+      const Grid gg = make_grid<T>(n_eval, nt, Rc, W, nfk, depth_c, 0, ds->w != nullptr, ctx->tree_group, mrb);
       *rb_rows = int64_t(gg.tiles) * 64 * Rc;
       return int64_t(gg.n_row_blocks) * *rb_rows;
     };
@@ -787,7 +846,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
     // blocks); decided on that grid whatever max_row_blocks says, so the knob never changes a result.
     int64_t rb_big = 0;
     {
-      const Grid gb = make_grid<T>(max_shard, nt, R, W, int(ds->nf), 1, 0, ds->w != nullptr, ctx->tree_group,
+      const Grid gb = make_grid<T>(max_shard, nt, R, W, nfk, 1, 0, ds->w != nullptr, ctx->tree_group,
                                    std::max<int64_t>(512, (max_shard + ctx->fold_seg_max - 1) / std::max<int64_t>(1, ctx->fold_seg_max)));
       rb_big = int64_t(gb.tiles) * 64 * R;
     }
@@ -932,6 +991,8 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
   if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_start, s));
   if (gather)
     SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, row_idx, size_t(n_rows_up) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  if (parametric && nt > 0 && p_stride > 0)  // (ahead of the chunks' join: both streams see the table)
+    SR_HIP_CHECK(hipMemcpyAsync(ctx->ptab.p, ctx->h_ptab.p, size_t(nt) * size_t(p_stride) * sizeof(T), hipMemcpyHostToDevice, s));
   // derived columns (LOAD_DERIVED): for the BASIC-tier deferred-check loss kernels over many rows,
   // every unary(feature) node of a transcendental shared by several trees is evaluated once for the
   // call.  Chosen from a sample of the batch; not when the data itself needs tracked feature loads.
@@ -940,7 +1001,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
   const int64_t dld = (n_eval + kRowAlign - 1) / kRowAlign * kRowAlign;
   // (row-sharded calls pass `shard`: the choice then depends only on the trees and on statistics of
   // every shard, so all ranks compile the same programs and number their checked arrays alike)
-  const double max_abs_x = shard ? shard->max_abs_x : ds->max_abs_x;
+  const double max_abs_x = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
   const int64_t derived_rows = shard ? shard->min_rows : n_eval;
   // (and only for calls with enough work: the column pass is one more launch, which a search's small
   // calls — tens of trees x 1e5 rows — would pay in latency for nothing)
@@ -1018,8 +1079,11 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
     sub.offsets = trees->offsets + t0;  // node arrays stay indexed by absolute offsets
     SrProgramBatch<T> pc;
     pc.keep_pieces = true;  // (staged below straight from the compile workers' buffers)
+    // (a parametric batch's per-node arrays are indexed by absolute node offsets, like the tree batch's)
+    const SrParamNodes pnodes{parametric ? pb->is_parameter : nullptr, parametric ? pb->parameter : nullptr,
+                              parametric ? pb->max_parameters : 0};
     int rc = sr_compile_batch<T>(sub, ctx->opsets[opset_id], n_total, ds->nf, false, &pc, &err,
-                                 dmap.empty() ? nullptr : dmap.data());
+                                 dmap.empty() ? nullptr : dmap.data(), parametric ? &pnodes : nullptr);
     if (rc != SR_OK) {
       sync_both();  // earlier chunks may still read the staging buffers
       if (rc == SR_ERR_BAD_TREE || rc == SR_ERR_INVALID_ARG) {
@@ -1083,7 +1147,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       if (sort && ctx->balance_groups && !multi) {
         auto deal = [&](int64_t p0, int64_t np, int Rc, int depth_c) {
           if (np <= 1) return;
-          const Grid gc = make_grid<T>(n_eval, np, Rc, W, int(ds->nf), depth_c, 0, ds->w != nullptr, ctx->tree_group,
+          const Grid gc = make_grid<T>(n_eval, np, Rc, W, nfk, depth_c, 0, ds->w != nullptr, ctx->tree_group,
                                        mrb);
           const int64_t G = gc.G, ng = gc.n_groups;
           if (ng <= 1) return;
@@ -1134,7 +1198,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
     int n_seg = 0;
     int64_t seg_blocks = 0;
     if (multi && nc > 0) {
-      const Grid gm = make_grid<T>(n_eval, nc, R, W, int(ds->nf), depth, 0, ds->w != nullptr, ctx->tree_group,
+      const Grid gm = make_grid<T>(n_eval, nc, R, W, nfk, depth, 0, ds->w != nullptr, ctx->tree_group,
                                    mrb);
       SrSegment* hs = reinterpret_cast<SrSegment*>(hprog + o_seg);
       for (int64_t p = 0; p < nc;) {
@@ -1178,7 +1242,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
     // [n_rb][np] words from p0 * n_rb (the chunk's region holds n_rb rows for every position)
     auto launch = [&](int64_t p0, int64_t np, bool vstk) -> int {
       const int Rc = vstk ? Rv : R;
-      Grid g = make_grid<T>(n_eval, np, Rc, W, int(ds->nf), vstk ? 0 : depth, 0, ds->w != nullptr, ctx->tree_group,
+      Grid g = make_grid<T>(n_eval, np, Rc, W, nfk, vstk ? 0 : depth, 0, ds->w != nullptr, ctx->tree_group,
                            mrb);
       if (g.lds > kLdsMax)
         return set_error(SR_ERR_TOO_DEEP, "the row tile (" + std::to_string(ds->nf) + " features, " +
@@ -1203,7 +1267,13 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       a.derived = dmap.empty() ? nullptr : ctx->derived_cols.as<T>();
       a.dld = dld;
       a.n_rows = n_eval;
-      a.nf = int(ds->nf);
+      a.nf = nfk;
+      SrParamArgs<T> pa_{};
+      if (parametric) {  // (the chunk's rows of the table: the kernel indexes it by the chunk-local tree index)
+        pa_.ptab = ctx->ptab.as<T>() + size_t(t0) * size_t(p_stride);
+        pa_.p_stride = int(p_stride);
+        pa_.n_classes = int(pb->n_classes);
+      }
       a.tiles_per_block = g.tiles;
       a.n_row_blocks = g.n_row_blocks;
       a.n_groups = g.n_groups;
@@ -1318,7 +1388,10 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
             pa.dld = kProbeRows;
           }
         }
-        SR_HIP_CHECK(sr_launch_eval<T>(pa, mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles, cs));
+        if (parametric)
+          SR_HIP_CHECK(sr_launch_eval_param<T>(pa, pa_, mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles, cs));
+        else
+          SR_HIP_CHECK(sr_launch_eval<T>(pa, mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles, cs));
       }
 #ifdef SR_STAMPS
       ctx->n_stamps = g.n_blocks * g.W * SR_NSTAMPS;
@@ -1326,8 +1399,11 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       SR_HIP_CHECK(hipMemsetAsync(ctx->stamps.p, 0, size_t(ctx->n_stamps) * sizeof(uint64_t), cs));
       a.stamps = ctx->stamps.as<uint64_t>();
 #endif
-      SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
-      if (fold_path) fjob.regions.push_back({a, t0, t0 + p0, np, n_blocks, Rc, vstk, g});
+      if (parametric)
+        SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
+      else
+        SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
+      if (fold_path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g});
       if (!direct && !fused && host_red)
         ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
       else if (!direct && !fused && !fjob.fuse_reduce)
@@ -1599,7 +1675,11 @@ int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, 
     const char* v = std::getenv("SR_AMD_EXACT_TIER");
     return v && std::strcmp(v, "full") == 0;
   }();
-  const int etier = (prog.tier == SR_TIER_BASIC && !exact_full) ? SR_TIER_BASIC : SR_TIER_FULL;
+  // a parametric call (sr_ctx::param, the table of its run_batch still on the device): the PARAM builds
+  // of the pass — the FULL-tier build, 4 waves — over the staged rows with the hidden class row
+  const sr_param_batch* const pb = ctx->param;
+  const int nfk = int(ds->nf) + (pb ? 1 : 0);
+  const int etier = (prog.tier == SR_TIER_BASIC && !exact_full && !pb) ? SR_TIER_BASIC : SR_TIER_FULL;
   const int64_t n_ranges = int64_t(ranges.size());
   int64_t max_len = 1;
   std::vector<int64_t> lo(static_cast<size_t>(n_ranges)), hi(static_cast<size_t>(n_ranges));
@@ -1666,13 +1746,13 @@ int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, 
     int G = int(std::min<int64_t>(nb, ctx->exact_g > 0 ? ctx->exact_g : std::max<int64_t>(1, std::min<int64_t>(16, g_fill))));
     // four waves per workgroup share the staged rows, each folding its own trees: one wave per
     // workgroup left ~1 wave per SIMD for C2's 8 listed trees x 1024 leaves (latency-bound)
-    int W = (ctx->exact_w == 4 && G >= 4) ? 4 : 1;
+    int W = ((ctx->exact_w == 4 && G >= 4) || pb) ? 4 : 1;
     size_t lds = 0;
     for (;;) {
-      lds = sr_tile_lds_bytes(int(sizeof(T)), int(ds->nf), R, depth, G, max_checks, W, false);
+      lds = sr_tile_lds_bytes(int(sizeof(T)), nfk, R, depth, G, max_checks, W, false);
       if (lds <= kLdsMax || G == 1) break;
       G /= 2;
-      if (G < W) W = 1;
+      if (G < W && !pb) W = 1;
     }
     if (lds > kLdsMax) return set_error(SR_ERR_TOO_DEEP, "exact-sum pass needs more LDS than 160 KiB");
     uint32_t* list32 = reinterpret_cast<uint32_t*>(hx + o_list);  // (the previous batch's pass has completed)
@@ -1693,7 +1773,13 @@ int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, 
     a.row_idx = gather ? ctx->row_idx.as<int64_t>() + dev_row_off : nullptr;  // (this view's rows on the device)
     a.ld = ds->ld;
     a.n_rows = n_eval;
-    a.nf = int(ds->nf);
+    a.nf = nfk;
+    SrParamArgs<T> pa_{};
+    if (pb) {
+      pa_.ptab = ctx->ptab.as<T>();
+      pa_.p_stride = int(pb->max_parameters) * int(pb->n_classes);
+      pa_.n_classes = int(pb->n_classes);
+    }
     a.tiles_per_block = int((max_len + rows - 1) / rows);
     a.n_row_blocks = int(n_ranges);
     a.n_groups = int((nb + G - 1) / G);
@@ -1706,7 +1792,10 @@ int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, 
     const int64_t blocks = int64_t(a.n_groups) * n_ranges;
     if (blocks > 0x7fffffff) return set_error(SR_ERR_INVALID_ARG, "grid too large");
     SR_HIP_CHECK(hipEventRecord(ctx->ev_k0, s));
-    SR_HIP_CHECK(sr_launch_eval<T>(a, SR_MODE_EXACT, gather, etier, R, W, false, int(blocks), s));
+    if (pb)
+      SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, SR_MODE_EXACT, gather, etier, R, W, false, int(blocks), s));
+    else
+      SR_HIP_CHECK(sr_launch_eval<T>(a, SR_MODE_EXACT, gather, etier, R, W, false, int(blocks), s));
     if (host_finite) {
       const int64_t n_arrays = nb * max_checks;
       SR_HIP_CHECK(ctx->jsum_scratch.ensure(size_t(std::max<int64_t>(1, n_arrays * n_internal)) * sizeof(T)));
@@ -1840,6 +1929,39 @@ struct SubBatch {
   }
 };
 
+// The parameter side of the same trees (a parametric call's fold passes): node arrays and matrices copied
+// alike; `swap` installs it as the context's running parametric batch until it goes out of scope.
+template <typename T>
+struct SubParam {
+  std::vector<uint8_t> isp;
+  std::vector<uint16_t> par;
+  std::vector<T> mats;
+  sr_param_batch b{};
+  sr_ctx* ctx = nullptr;
+  const sr_param_batch* saved = nullptr;
+  SubParam(sr_ctx* c, const sr_tree_batch& trees, const int64_t* idx, size_t n) : ctx(c), saved(c->param) {
+    if (!saved) return;
+    const size_t stride = size_t(saved->max_parameters) * size_t(saved->n_classes);
+    const T* src = static_cast<const T*>(saved->parameters);
+    mats.resize(n * stride + 1);
+    for (size_t i = 0; i < n; ++i) {
+      const int64_t b0 = trees.offsets[idx[i]], len = trees.offsets[idx[i] + 1] - b0;
+      isp.insert(isp.end(), saved->is_parameter + b0, saved->is_parameter + b0 + len);
+      par.insert(par.end(), saved->parameter + b0, saved->parameter + b0 + len);
+      if (stride) std::memcpy(mats.data() + i * stride, src + size_t(idx[i]) * stride, stride * sizeof(T));
+    }
+    if (isp.empty()) {  // (non-NULL arrays for an empty list)
+      isp.push_back(0);
+      par.push_back(0);
+    }
+    b = sr_param_batch{isp.data(), par.data(), saved->max_parameters, saved->n_classes, mats.data()};
+    ctx->param = &b;
+  }
+  ~SubParam() { ctx->param = saved; }
+  SubParam(const SubParam&) = delete;
+  SubParam& operator=(const SubParam&) = delete;
+};
+
 // Rows per segment of the fold's segmented chain (sr_aux.hip): ctx->fold_seg < 0 chooses (<= 1024
 // segments of 8k-64k rows), 0 folds the whole view with one workgroup scan per tree (rounds 3-4).
 inline int64_t fold_seg_len(const sr_ctx* ctx, int64_t n) {
@@ -1937,6 +2059,7 @@ int fold_prepare(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_
   const bool gather = row_idx != nullptr && n_idx > 0;
   const int64_t n_eval = gather ? n_idx : ds->n;
   SubBatch<T> sub(*trees, list, nb);
+  SubParam<T> subp(ctx, *trees, list, nb);  // (a parametric call: these trees' parameter side, for this pass)
   SrProgramBatch<T> prog;
   Grid g;
   SR_HIP_CHECK(hipEventRecord(ctx->ev_f[0], ctx->stream));
@@ -2371,8 +2494,11 @@ std::vector<int64_t> stress_rows(const T* X, int64_t nf, int64_t n) {
 }
 
 template <typename T>
-int upload_impl(sr_ctx* ctx, const void* X, int64_t nf, int64_t n, const void* y, const void* w, sr_dataset** out) {
+int upload_impl(sr_ctx* ctx, const void* X, int64_t nf, int64_t n, const void* y, const void* w, sr_dataset** out,
+                const int32_t* cls = nullptr, int32_t n_classes = 0) {
   auto* ds = new sr_dataset();
+  ds->n_classes = cls ? n_classes : 0;
+  const int64_t nf_dev = nf + (cls ? 1 : 0);  // (the hidden class row after the user's features)
   ds->ctx = ctx;
   ds->dtype = sizeof(T) == 4 ? SR_DTYPE_F32 : SR_DTYPE_F64;
   ds->nf = nf;
@@ -2399,7 +2525,7 @@ int upload_impl(sr_ctx* ctx, const void* X, int64_t nf, int64_t n, const void* y
     ds->max_abs_x = bad ? double(INFINITY) : m;
   }
   hipError_t e;
-  if ((e = hipMalloc(&ds->X, size_t(nf) * size_t(ds->ld) * sizeof(T))) != hipSuccess) return fail(e, "hipMalloc X");
+  if ((e = hipMalloc(&ds->X, size_t(nf_dev) * size_t(ds->ld) * sizeof(T))) != hipSuccess) return fail(e, "hipMalloc X");
   void* tmp = nullptr;
   if ((e = hipMalloc(&tmp, size_t(nf) * size_t(n) * sizeof(T))) != hipSuccess) return fail(e, "hipMalloc staging");
   if ((e = hipMemcpyAsync(tmp, X, size_t(nf) * size_t(n) * sizeof(T), hipMemcpyHostToDevice, s)) != hipSuccess) {
@@ -2415,6 +2541,14 @@ int upload_impl(sr_ctx* ctx, const void* X, int64_t nf, int64_t n, const void* y
     return fail(e, "sync");
   }
   (void)hipFree(tmp);
+  if (cls) {
+    // the class row: 0-based ids in T (exact: n_classes < 2^24), padded like every X row with row 0's value
+    std::vector<T> row(static_cast<size_t>(ds->ld));
+    for (int64_t i = 0; i < ds->ld; ++i) row[size_t(i)] = T(cls[i < n ? i : 0] - 1);
+    if ((e = hipMemcpy(static_cast<T*>(ds->X) + size_t(nf) * size_t(ds->ld), row.data(), row.size() * sizeof(T),
+                       hipMemcpyHostToDevice)) != hipSuccess)
+      return fail(e, "copy classes");
+  }
   if (y) {
     if ((e = hipMalloc(&ds->y, size_t(ds->ld) * sizeof(T))) != hipSuccess) return fail(e, "hipMalloc y");
     if ((e = hipMemcpyAsync(ds->y, y, size_t(n) * sizeof(T), hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "copy y");
@@ -3639,9 +3773,9 @@ int sr_shutdown(sr_ctx* ctx) {
                       &ctx->hint, &ctx->jsum_prog, &ctx->jsum_scratch, &ctx->probe_sum, &ctx->probe_flag, &ctx->g_code, &ctx->g_offsets, &ctx->g_consts, &ctx->g_const_off,
                       &ctx->g_items, &ctx->g_part, &ctx->g_out, &ctx->derived_cols, &ctx->probe_derived, &ctx->coll_buf, &ctx->coll_packed, &ctx->ctl, &ctx->fold_io, &ctx->group_cnt,
                       &ctx->fold_code, &ctx->fold_tab, &ctx->fold_store, &ctx->fold_ctl, &ctx->fold_io2, &ctx->fold_sq,
-                      &ctx->fold_tab2})
+                      &ctx->fold_tab2, &ctx->ptab})
       b->release();
-    for (HostBuf* b : {&ctx->h_prog, &ctx->h_outs, &ctx->h_grad, &ctx->h_coll, &ctx->h_part, &ctx->h_exact})
+    for (HostBuf* b : {&ctx->h_prog, &ctx->h_outs, &ctx->h_grad, &ctx->h_coll, &ctx->h_part, &ctx->h_exact, &ctx->h_ptab})
       b->release();
     for (int c = 0; c < kMaxChunks; ++c) {
       (void)hipEventDestroy(ctx->ev_c0[c]);
@@ -3722,6 +3856,23 @@ int sr_dataset_upload(sr_ctx* ctx, int dtype, const void* X, int64_t nfeatures, 
   return set_error(SR_ERR_INVALID_ARG, "unknown dtype");
 }
 
+int sr_dataset_upload_classes(sr_ctx* ctx, int dtype, const void* X, int64_t nfeatures, int64_t n, const void* y,
+                              const void* weights, const int32_t* cls, int32_t n_classes, sr_dataset** out) {
+  if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
+  if (!out || !X || nfeatures <= 0 || n <= 0) return set_error(SR_ERR_INVALID_ARG, "bad dataset arguments");
+  if (nfeatures > 65534) return set_error(SR_ERR_INVALID_ARG, "nfeatures (with the class row) exceeds Node.feature (UInt16)");
+  if (!cls || n_classes < 1 || n_classes >= (1 << 24)) return set_error(SR_ERR_INVALID_ARG, "bad class column");
+  for (int64_t i = 0; i < n; ++i)
+    if (cls[i] < 1 || cls[i] > n_classes)
+      return set_error(SR_ERR_INVALID_ARG, "row " + std::to_string(i) + ": class " + std::to_string(cls[i]) +
+                                               " outside 1.." + std::to_string(n_classes));
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  if (dtype == SR_DTYPE_F32) return upload_impl<float>(ctx, X, nfeatures, n, y, weights, out, cls, n_classes);
+  if (dtype == SR_DTYPE_F64) return upload_impl<double>(ctx, X, nfeatures, n, y, weights, out, cls, n_classes);
+  return set_error(SR_ERR_INVALID_ARG, "unknown dtype");
+}
+
 int sr_dataset_free(sr_dataset* ds) {
   if (!ds) return SR_OK;
   if (ds->ctx) {
@@ -3762,6 +3913,41 @@ int sr_eval_loss_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr
   return eval_loss_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete);
 }
 
+// The parametric entry points: the plain call with the batch's parameter side installed in the context
+// for its duration (run_batch and the passes after it read sr_ctx::param).
+namespace {
+struct ParamScope {
+  sr_ctx* ctx;
+  ParamScope(sr_ctx* c, const sr_param_batch* p) : ctx(c) { c->param = p; }
+  ~ParamScope() { ctx->param = nullptr; }
+};
+int check_params(const sr_dataset* ds, const sr_tree_batch* trees, const sr_param_batch* params) {
+  if (!params) return set_error(SR_ERR_INVALID_ARG, "NULL parameter batch");
+  if (ds->n_classes <= 0) return set_error(SR_ERR_INVALID_ARG, "a parametric call needs a dataset uploaded with classes");
+  if (params->n_classes != ds->n_classes)
+    return set_error(SR_ERR_INVALID_ARG, "sr_param_batch n_classes " + std::to_string(params->n_classes) +
+                                             " differs from the dataset's " + std::to_string(ds->n_classes));
+  if (params->max_parameters < 0 || params->max_parameters > 65535) return set_error(SR_ERR_INVALID_ARG, "bad max_parameters");
+  if (trees->n_trees > 0 && (!params->is_parameter || !params->parameter || (params->max_parameters > 0 && !params->parameters)))
+    return set_error(SR_ERR_INVALID_ARG, "sr_param_batch has NULL arrays");
+  return SR_OK;
+}
+}  // namespace
+
+int sr_eval_loss_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind,
+                                  void* out_loss, uint8_t* out_complete) {
+  int rc = validate_common(ctx, ds, opset_id, trees);
+  if (rc != SR_OK) return rc;
+  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  ParamScope scope(ctx, params);
+  if (ds->dtype == SR_DTYPE_F32)
+    return eval_loss_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete);
+  return eval_loss_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete);
+}
+
 // several row views in one call (per-island minibatches): validated here, ViewSpec below the ABI
 static int check_views(const sr_tree_batch* trees, const int32_t* tree_view, int n_views, const int64_t* view_rows,
                        int64_t view_len) {
@@ -3783,6 +3969,38 @@ int sr_eval_loss_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, co
   if (ds->dtype == SR_DTYPE_F32)
     return eval_loss_impl<float>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
   return eval_loss_impl<double>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
+}
+
+int sr_eval_loss_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                        const sr_param_batch* params, const int32_t* tree_view, int n_views,
+                                        const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
+                                        uint8_t* out_complete) {
+  int rc = validate_common(ctx, ds, opset_id, trees);
+  if (rc != SR_OK) return rc;
+  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
+  if ((rc = check_views(trees, tree_view, n_views, view_rows, view_len)) != SR_OK) return rc;
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  ParamScope scope(ctx, params);
+  const ViewSpec vs{tree_view, n_views, view_len};
+  const ViewSpec* v = n_views > 1 ? &vs : nullptr;
+  if (ds->dtype == SR_DTYPE_F32)
+    return eval_loss_impl<float>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
+  return eval_loss_impl<double>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
+}
+
+int sr_eval_tree_array_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, void* out_pred,
+                                  uint8_t* out_complete) {
+  int rc = validate_common(ctx, ds, opset_id, trees);
+  if (rc != SR_OK) return rc;
+  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  ParamScope scope(ctx, params);
+  if (ds->dtype == SR_DTYPE_F32)
+    return eval_pred_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, out_pred, out_complete);
+  return eval_pred_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, out_pred, out_complete);
 }
 
 int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
@@ -4175,10 +4393,10 @@ int sr_eval_grad_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr
   return eval_grad_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_grad, out_complete);
 }
 
-int sr_compile_info(int dtype, int n_unary, const char* const* unary_names, int n_binary,
-                    const char* const* binary_names, const sr_tree_batch* trees, int64_t n_rows,
-                    int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
-                    void* out_code, int64_t code_capacity) {
+static int compile_info_impl(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                             const char* const* binary_names, const sr_tree_batch* trees, const SrParamNodes* pn,
+                             int64_t n_rows, int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad,
+                             int32_t* out_max_depth, void* out_code, int64_t code_capacity) {
   if (!trees || n_unary < 0 || n_binary < 0 || (n_unary > 0 && !unary_names) || (n_binary > 0 && !binary_names))
     return set_error(SR_ERR_INVALID_ARG, "bad arguments");
   SrOpset o;
@@ -4210,17 +4428,37 @@ int sr_compile_info(int dtype, int n_unary, const char* const* unary_names, int 
   };
   if (dtype == SR_DTYPE_F32) {
     SrProgramBatch<float> prog;
-    int rc = sr_compile_batch<float>(*trees, o, n_rows, nfeatures, false, &prog, &err);
+    int rc = sr_compile_batch<float>(*trees, o, n_rows, nfeatures, false, &prog, &err, nullptr, pn);
     if (rc != SR_OK) return set_error(rc, err);
     return report(prog);
   }
   if (dtype == SR_DTYPE_F64) {
     SrProgramBatch<double> prog;
-    int rc = sr_compile_batch<double>(*trees, o, n_rows, nfeatures, false, &prog, &err);
+    int rc = sr_compile_batch<double>(*trees, o, n_rows, nfeatures, false, &prog, &err, nullptr, pn);
     if (rc != SR_OK) return set_error(rc, err);
     return report(prog);
   }
   return set_error(SR_ERR_INVALID_ARG, "unknown dtype");
+}
+
+int sr_compile_info(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                    const char* const* binary_names, const sr_tree_batch* trees, int64_t n_rows,
+                    int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
+                    void* out_code, int64_t code_capacity) {
+  return compile_info_impl(dtype, n_unary, unary_names, n_binary, binary_names, trees, nullptr, n_rows, nfeatures,
+                           out_len, out_static_bad, out_max_depth, out_code, code_capacity);
+}
+
+int sr_compile_info_parametric(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                               const char* const* binary_names, const sr_tree_batch* trees,
+                               const sr_param_batch* params, int64_t n_rows, int64_t nfeatures, int32_t* out_len,
+                               uint8_t* out_static_bad, int32_t* out_max_depth, void* out_code,
+                               int64_t code_capacity) {
+  if (!params) return set_error(SR_ERR_INVALID_ARG, "NULL parameter batch");
+  if (params->max_parameters < 0 || params->max_parameters > 65535) return set_error(SR_ERR_INVALID_ARG, "bad max_parameters");
+  const SrParamNodes pn{params->is_parameter, params->parameter, params->max_parameters};
+  return compile_info_impl(dtype, n_unary, unary_names, n_binary, binary_names, trees, &pn, n_rows, nfeatures, out_len,
+                           out_static_bad, out_max_depth, out_code, code_capacity);
 }
 
 int sr_host_unary(int dtype, const char* name, int64_t n, const void* x, void* out) {

@@ -154,6 +154,9 @@ struct Tree {
   const uint8_t* constant;
   const T* val;
   int64_t n;
+  // ParametricExpression batches (NULL otherwise): per node, is this leaf a parameter, and which (1-based)
+  const uint8_t* is_param = nullptr;
+  const uint16_t* param = nullptr;
 };
 
 // v[0..n) = x, growing v only when it is too short (the compiler's per-tree arrays keep their
@@ -186,6 +189,7 @@ struct TreeCompiler {
   int64_t n_ops = 0;
 
   const int16_t* derived = nullptr;  // [SR_U_COUNT][nfeatures]: derived column of unary(feature), -1 none
+  int max_params = 0;                // parameter leaves name p1 .. p<max_params>
   // constant-operand binaries fused as PBC fields (SR_AMD_PBC=0 turns it off: A/B runs)
   const bool fuse_pbc = [] {
     static const bool on = [] {
@@ -203,13 +207,16 @@ struct TreeCompiler {
   int derived_col(int i) {
     if (!derived || t.degree[i] != 1) return -1;
     const int c = t.l[i];
-    if (t.degree[c] != 0 || t.constant[c]) return -1;
+    if (t.degree[c] != 0 || t.constant[c] || par(c)) return -1;
     const uint32_t u = unary_id(i);
     if (u == SR_U_NONE || u >= SR_U_COUNT) return -1;
     return derived[size_t(u) * size_t(nfeatures) + size_t(t.feature[c] - 1)];
   }
 
   bool leaf(int i) const { return t.degree[i] == 0; }
+  // a parameter leaf: a feature leaf in every decision below (DynamicExpressions evaluates it as feature
+  // nfeatures + k of [X; parameters[:, class]]); only the instruction that reads it differs
+  bool par(int i) const { return t.is_param != nullptr && t.is_param[i] != 0; }
   bool effleaf(int i) const { return t.degree[i] == 0 || folded[i]; }
 
   uint32_t unary_id(int i) {
@@ -254,7 +261,18 @@ struct TreeCompiler {
       const int d = t.degree[i];
       if (d == 0) {
         sz[i] = 1;
-        if (t.constant[i]) {
+        if (par(i)) {
+          is_const[i] = 0;
+          if (t.constant[i]) {
+            fail(SR_ERR_BAD_TREE, "a parameter leaf marked constant");
+            return false;
+          }
+          const int k = int(t.param[i]);
+          if (k < 1 || k > max_params) {
+            fail(SR_ERR_BAD_TREE, "parameter index out of range");
+            return false;
+          }
+        } else if (t.constant[i]) {
           is_const[i] = 1;
         } else {
           is_const[i] = 0;
@@ -268,6 +286,10 @@ struct TreeCompiler {
       }
       if (d > 2) {
         fail(SR_ERR_BAD_TREE, "degree > 2");
+        return false;
+      }
+      if (par(i)) {
+        fail(SR_ERR_BAD_TREE, "a parameter on an operator node");
         return false;
       }
       const int64_t a = i + 1;
@@ -409,6 +431,9 @@ struct TreeCompiler {
       in.op = SR_OP_LOAD_CONST;
       in.set_value(t.val[i]);
       if (with_const_index) in.meta = uint32_t(const_slot[i]);
+    } else if (par(i)) {
+      in.op = SR_OP_LOAD_PARAM;
+      in.meta = uint32_t(t.param[i]) - 1u;
     } else {
       in.op = SR_OP_LOAD_FEAT;
       in.meta = uint32_t(t.feature[i]) - 1u;
@@ -420,6 +445,10 @@ struct TreeCompiler {
     SrIns<T> in = leaf_ins(i);
     const bool is_const = in.op == SR_OP_LOAD_CONST;
     if (commutes(bop)) left = false;  // IEEE + and * commute: one variant per operand kind
+    if (in.op == SR_OP_LOAD_PARAM) {
+      in.op = SR_PBIN_OPC(bop, left ? SR_V_PL : SR_V_PR);
+      return in;
+    }
     const uint32_t v = is_const ? (left ? SR_V_CL : SR_V_CR) : (left ? SR_V_FL : SR_V_FR);
     in.op = SR_BIN_OPC(bop, v);
     return in;
@@ -452,6 +481,7 @@ struct TreeCompiler {
     const uint32_t base = in.op & SR_OP_MASK;  // (a fused POST unary sits above the opcode)
     if (base >= SR_OP_PAIR0) in.op += SR_P_PUSH;                     // PAIR v -> PAIR v + PUSH
     else if (base == SR_OP_LOAD_DERIVED) in.op += SR_OP_LOAD_DERIVED_PUSH - SR_OP_LOAD_DERIVED;
+    else if (base == SR_OP_LOAD_PARAM) in.op += SR_OP_LOAD_PARAM_PUSH - SR_OP_LOAD_PARAM;
     else in.op += SR_OP_LOAD_FEAT_PUSH - SR_OP_LOAD_FEAT;             // LOAD_x -> LOAD_x_PUSH
     in.meta |= uint32_t(slot + 1) << SR_M_PUSH_SHIFT;
   }
@@ -462,6 +492,7 @@ struct TreeCompiler {
   bool emit_pair(int i, uint32_t bop) {
     const int a = t.l[i], b = t.r[i];
     if (with_const_index || !effleaf(a) || !effleaf(b)) return false;
+    if (par(a) || par(b)) return false;  // (no pair forms with a parameter: its LOAD, then the other operand)
     SrIns<T> la = leaf_ins(a), lb = leaf_ins(b);
     const bool ca = la.op == SR_OP_LOAD_CONST, cb = lb.op == SR_OP_LOAD_CONST;
     if (ca && cb) return false;  // (only when folding is off)
@@ -514,7 +545,8 @@ struct TreeCompiler {
     const uint32_t base = last.op & SR_OP_MASK;
     const bool free_c = base == SR_OP_LOAD_FEAT || base == SR_OP_LOAD_FEAT_PUSH ||
                         (base >= SR_OP_UNARY0 && base < SR_OP_LOAD_DERIVED) ||
-                        (base >= SR_OP_BINARY0 && base < SR_OP_PAIR0 && (base - SR_OP_BINARY0) % 6u < SR_V_CL);
+                        (base >= SR_OP_BINARY0 && base < SR_OP_LOAD_PARAM && (base - SR_OP_BINARY0) % 6u < SR_V_CL) ||
+                        (base >= SR_OP_LOAD_PARAM && base < SR_OP_PAIR0);  // (LOAD_PARAM / P binaries: the index only)
     if (!free_c) return false;
     uint32_t v = 0;
     switch (bop) {
@@ -579,7 +611,9 @@ struct TreeCompiler {
     if (err != SR_OK) return;
     if (emit_pair(i, bop)) {
       // both operands in one instruction
-    } else if (effleaf(b)) {  // op(tos = left, operand = right leaf)
+    } else if (effleaf(b) && !(par(b) && effleaf(a) && !par(a))) {  // op(tos = left, operand = right leaf)
+      // (constant op parameter: the parameter's LOAD first, the constant as its operand below — a
+      //  LOAD_CONST is only ever a constant tree's root)
       emit(a);
       if (fuse_const_operand(i, b, bop, false)) return;
       const_operand_check(b);
@@ -621,6 +655,8 @@ struct TreeCompiler {
     t.constant = tree.constant;
     t.val = tree.val;
     t.n = tree.n;
+    t.is_param = tree.is_param;
+    t.param = tree.param;
     code.clear();
     bad = false;
     err = SR_OK;
@@ -675,6 +711,11 @@ static uint32_t sr_instruction_cost_slow(uint32_t code) {
   code &= SR_OP_MASK;
   if (code == SR_OP_LOAD_FEAT_PUSH || code == SR_OP_LOAD_CONST_PUSH || code == SR_OP_LOAD_DERIVED_PUSH) c += 2;
   if (code == SR_OP_LOAD_DERIVED || code == SR_OP_LOAD_DERIVED_PUSH) return c + 3;
+  if (code == SR_OP_LOAD_PARAM || code == SR_OP_LOAD_PARAM_PUSH) return c + 6 + (code == SR_OP_LOAD_PARAM_PUSH ? 2u : 0u);
+  if (code >= SR_OP_PBIN0 && code < SR_OP_PAIR0) {  // a gathered operand, then priced as its binary operator
+    c += 6;
+    code = SR_OP_BINARY0 + (code - SR_OP_PBIN0) / 2u * 6u;
+  }
   if (code >= SR_OP_PAIR0) {
     c += ((code - SR_OP_PAIR0) % 6u >= SR_P_PUSH) ? 3 : 1;  // second operand (+ push)
     code = SR_OP_BINARY0 + (code - SR_OP_PAIR0) / 6u * 6u;  // priced as its binary operator
@@ -731,8 +772,17 @@ void sr_parallel_for(int n, const std::function<void(int)>& fn) {
 
 template <typename T>
 int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_rows, int64_t nfeatures,
-                     bool with_const_index, SrProgramBatch<T>* out, std::string* err, const int16_t* derived) {
+                     bool with_const_index, SrProgramBatch<T>* out, std::string* err, const int16_t* derived,
+                     const SrParamNodes* pn) {
   const int64_t nt = trees.n_trees;
+  if (pn && nt > 0 && (!pn->is_parameter || !pn->parameter || pn->max_parameters < 0)) {
+    *err = "sr_param_batch has NULL arrays";
+    return SR_ERR_INVALID_ARG;
+  }
+  if (pn && with_const_index) {
+    *err = "gradient programs take no parameter leaves";
+    return SR_ERR_INVALID_ARG;
+  }
   if (nt < 0 || (nt > 0 && (!trees.offsets || !trees.degree || !trees.op || !trees.feature ||
                             !trees.constant || !trees.val))) {
     *err = "sr_tree_batch has NULL arrays";
@@ -767,6 +817,7 @@ int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_r
 
   auto work = [&](int w, int64_t lo, int64_t hi) {
     TreeCompiler<T> tc(ops, n_rows, nfeatures, with_const_index, with_const_index ? nullptr : derived);
+    if (pn) tc.max_params = pn->max_parameters;
     std::vector<SrIns<T>>& buf = bufs[size_t(w)];
     buf.reserve(size_t(trees.offsets[hi] - trees.offsets[lo]));
     for (int64_t k = lo; k < hi; ++k) {
@@ -782,6 +833,10 @@ int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_r
       tree.constant = trees.constant + b;
       tree.val = vals + b;
       tree.n = e - b;
+      if (pn) {
+        tree.is_param = pn->is_parameter + b;
+        tree.param = pn->parameter + b;
+      }
       tc.run(tree);
       if (tc.err != SR_OK) {
         errs[k] = tc.err;
@@ -867,6 +922,6 @@ int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_r
 }
 
 template int sr_compile_batch<float>(const sr_tree_batch&, const SrOpset&, int64_t, int64_t, bool,
-                                     SrProgramBatch<float>*, std::string*, const int16_t*);
+                                     SrProgramBatch<float>*, std::string*, const int16_t*, const SrParamNodes*);
 template int sr_compile_batch<double>(const sr_tree_batch&, const SrOpset&, int64_t, int64_t, bool,
-                                      SrProgramBatch<double>*, std::string*, const int16_t*);
+                                      SrProgramBatch<double>*, std::string*, const int16_t*, const SrParamNodes*);

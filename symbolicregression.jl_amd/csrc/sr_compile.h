@@ -71,7 +71,15 @@ uint32_t sr_instruction_cost(uint32_t opcode);
 // derived: optional [SR_U_COUNT][nfeatures] map (-1 = none) of the call's derived columns; nodes
 // unary(feature) with a column become one LOAD_DERIVED (BASIC-tier LOSS programs only; ignored with
 // with_const_index).
+// pn: optional parameter leaves of a ParametricExpression batch (sr_param_batch's per-node arrays, parallel
+// to the tree batch's): such a leaf is a feature leaf to every decision of the compiler and becomes
+// LOAD_PARAM / a P binary operand (sr_ops.h); not with with_const_index.
+struct SrParamNodes {
+  const uint8_t* is_parameter;
+  const uint16_t* parameter;  // 1-based, <= max_parameters
+  int32_t max_parameters;
+};
 template <typename T>
 int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_rows, int64_t nfeatures,
                      bool with_const_index, SrProgramBatch<T>* out, std::string* err,
-                     const int16_t* derived = nullptr);
+                     const int16_t* derived = nullptr, const SrParamNodes* pn = nullptr);

@@ -19,6 +19,8 @@ enum { SR_MODE_LOSS = 0, SR_MODE_PRED = 1, SR_MODE_EXACT = 2, SR_MODE_FOLD = 3 }
 #define SR_VSTK_SLOTS 2
 #endif
 enum { SR_TIER_BASIC = 0, SR_TIER_FULL = 1 };
+// a flag on the tile kernel's tier template argument: the build for parametric calls (sr_tile_impl.h)
+enum { SR_TIER_PARAM = 2 };
 
 // One row view's launch positions in a several-view launch (sr_eval_loss_batch_views): positions
 // [pos0, pos0 + n_pos) in tree groups of trees_per_block, blocks [block0, block0 + groups x row blocks),
@@ -169,11 +171,27 @@ struct SrEvalArgs {
   // -DSR_STAMPS builds only (latency analysis, tools/stamps.py): per wave, SR_NSTAMPS wall-clock
   // stamps at fixed points of the kernel, [block][wave][SR_NSTAMPS]; NULL otherwise
   uint64_t* stamps;
+  // the builds for parametric calls (SR_TIER_PARAM, sr_inst_*param*.hip; no other kernel reads these,
+  // sr_launch_tile_param fills them from SrParamArgs)
+  const T* ptab;
+  int p_stride;
+  int n_classes;
+};
+// A parametric call's table: ptab[tree * p_stride + k * n_classes + class] at the caller's tree index (as
+// `offsets`).  The rows' 0-based classes are the last staged X row (the dataset's hidden row:
+// SrEvalArgs::nf counts it).
+template <typename T>
+struct SrParamArgs {
+  const T* ptab;
+  int p_stride;
+  int n_classes;
 };
 constexpr int SR_NSTAMPS = 8;
 
 template <typename T, int R, int MODE, bool GATHER, int TIER, int W = 4, int LK = -1, bool VSTK = false>
 hipError_t sr_launch_tile(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s);
+template <typename T, int R, int MODE, bool GATHER, int TIER, int W = 4, int LK = -1, bool VSTK = false>
+hipError_t sr_launch_tile_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int n_blocks, hipStream_t s);
 // LDS bytes one workgroup (W waves) of the tile kernel needs.
 size_t sr_tile_lds_bytes(int elem_size, int nf, int rows_per_lane, int stack_depth, int trees_per_block,
                          int max_checks, int waves, bool weighted, int code_lds = 0);
@@ -189,6 +207,14 @@ int sr_vstk_rows(int elem_size, int64_t n_rows, int requested);
 template <typename T>
 hipError_t sr_launch_eval(const SrEvalArgs<T>& a, int mode, bool gather, int tier, int R, int waves, bool vstk,
                           int n_blocks, hipStream_t s);
+// The same over the kernels built for parametric calls (LOAD_PARAM / P operands; sr_inst_*param*.hip), a
+// smaller set: Float32 BASIC loss at 8 rows per lane (classic, full view or gathered) and 16 (register
+// stack), Float64 at 4 and 8, the FULL tier at 4 / 2, PRED, EXACT with 4 waves (FULL-tier build) and the
+// Float32 FOLD builds of those loss launches; hipErrorInvalidValue for any other shape (the host maps a
+// parametric call's knobs onto this set: sr_capi.cpp run_batch).
+template <typename T>
+hipError_t sr_launch_eval_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int mode, bool gather, int tier, int R,
+                                int waves, bool vstk, int n_blocks, hipStream_t s);
 // Derived columns of a call (LOAD_DERIVED): column k = op[k](X[feat[k]]) over the view's rows.
 constexpr int SR_MAX_DERIVED = 32;
 struct SrDerivedSpec {

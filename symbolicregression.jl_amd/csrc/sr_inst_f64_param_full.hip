@@ -1,0 +1,6 @@
+// f64 FULL-tier loss and prediction kernels for parametric calls (2 rows/lane).
+#include "sr_tile_impl.h"
+SR_INSTANTIATE_PARAM(double, 2, SR_MODE_LOSS, false, SR_TIER_FULL, 4, -1, false)
+SR_INSTANTIATE_PARAM(double, 2, SR_MODE_LOSS, true, SR_TIER_FULL, 4, -1, false)
+SR_INSTANTIATE_PARAM(double, 2, SR_MODE_PRED, false, SR_TIER_FULL, 4, -1, false)
+SR_INSTANTIATE_PARAM(double, 2, SR_MODE_PRED, true, SR_TIER_FULL, 4, -1, false)

@@ -95,6 +95,13 @@ SR_HD inline bool sr_loss_propagates_nan(int32_t kind) {
 //           SR_P_FF: op(X[f], X[g])  SR_P_FC: op(X[f], c)  SR_P_CF: op(c, X[f])   (f in meta, g in c0)
 //           + SR_P_PUSH: the old tos is first stored to stack slot `push` (a subtree's first instruction)
 //         + and * never use CF (commuted to FC)
+//       SR_OP_LOAD_PARAM (_PUSH)  tos <- P_tree[k, class[row]]: a ParametricExpression's parameter leaf p_{k+1}
+//                             (k in the operand index): a gather from the call's per-tree parameter table by
+//                             the row's class, which the dataset keeps as one hidden extra row of X.  In every
+//                             other respect a feature leaf (checked like one, never folded); only the kernels
+//                             built for parametric calls (sr_inst_*param*.hip) implement it
+//       SR_OP_PBIN0 + 2*(b-1) + {SR_V_PL, SR_V_PR}   tos <- op_b(P[k], tos) / op_b(tos, P[k]): the parameter
+//                             leaf as a binary node's operand, as the F variants take a feature (+ and *: PR only)
 //       SR_OP_LOAD_DERIVED (_PUSH)  tos <- D[k]: a derived column op_u(X[f]) computed once per call
 //                             for the whole batch (LOSS programs of BASIC-tier kernels only: the
 //                             node unary(feature), shared by many trees of a population)
@@ -123,6 +130,10 @@ enum : uint32_t {
   SR_OP_UNARY_INF0 = 40u,  // opcode = SR_OP_UNARY_INF0 + SrUnaryOp (fused: non-finite input -> +Inf)
   SR_OP_BINARY0 = 80u,     // opcode = SR_OP_BINARY0 + 6*(SrBinaryOp-1) + variant
   SR_OP_LOAD_DERIVED = 78u, SR_OP_LOAD_DERIVED_PUSH = 79u,  // (between the unary-inf and binary ranges)
+  // (the free range between the binary and pair opcodes: parametric programs only)
+  SR_OP_LOAD_PARAM = 184u, SR_OP_LOAD_PARAM_PUSH = 185u,
+  SR_OP_PBIN0 = 186u,      // opcode = SR_OP_PBIN0 + 2*(SrBinaryOp-1) + SR_V_PL / SR_V_PR
+  SR_V_PL = 0u, SR_V_PR = 1u,
   SR_OP_PAIR0 = 256u,      // opcode = SR_OP_PAIR0 + 6*(SrBinaryOp-1) + pair variant
   SR_V_SL = 0u, SR_V_SR = 1u, SR_V_FL = 2u, SR_V_FR = 3u, SR_V_CL = 4u, SR_V_CR = 5u,
   SR_P_FF = 0u, SR_P_FC = 1u, SR_P_CF = 2u, SR_P_PUSH = 3u,
@@ -135,11 +146,14 @@ enum : uint32_t {
 static_assert(SR_OP_UNARY0 + SR_U_COUNT <= SR_OP_UNARY_INF0, "unary opcode ranges overlap");
 static_assert(SR_OP_UNARY_INF0 + SR_U_COUNT <= SR_OP_LOAD_DERIVED, "unary opcode range overlaps LOAD_DERIVED");
 static_assert(SR_OP_LOAD_DERIVED_PUSH < SR_OP_BINARY0, "LOAD_DERIVED overlaps the binary range");
-static_assert(SR_OP_BINARY0 + 6 * SR_B_COUNT <= SR_OP_PAIR0, "binary opcode range overlaps the pair range");
+static_assert(SR_OP_BINARY0 + 6 * SR_B_COUNT <= SR_OP_LOAD_PARAM, "binary opcode range overlaps LOAD_PARAM");
+static_assert(SR_OP_LOAD_PARAM_PUSH < SR_OP_PBIN0, "LOAD_PARAM overlaps the parameter-operand range");
+static_assert(SR_OP_PBIN0 + 2 * SR_B_COUNT <= SR_OP_PAIR0, "parameter-operand opcode range overlaps the pair range");
 static_assert(SR_OP_PAIR0 + 6 * SR_B_COUNT <= SR_OP_MASK + 1, "opcodes must fit the op word's low 9 bits");
 static_assert(SR_U_COUNT <= 64, "post-unary ids must fit 6 bits");
 #define SR_BIN_OPC(b, v) (SR_OP_BINARY0 + 6u * ((b) - 1u) + (v))
 #define SR_PAIR_OPC(b, v) (SR_OP_PAIR0 + 6u * ((b) - 1u) + (v))
+#define SR_PBIN_OPC(b, v) (SR_OP_PBIN0 + 2u * ((b) - 1u) + (v))
 
 template <typename T>
 struct alignas(16) SrIns {

@@ -668,6 +668,43 @@ constexpr bool sr_untracked_b(uint32_t) { return false; }
     }                                  \
     break;                             \
   }
+// PARAM builds: parameter `index` of the running tree (slot j of this wave) over the lane's R rows — each
+// row's 0-based class from the staged hidden row (the last of the a.nf staged rows; padded rows replicate
+// a real row, so every class is valid), then the tree's row k of the call's parameter table
+#define SR_PARAM_ROWS(o)                                                                                    \
+  {                                                                                                         \
+    T cls_[R];                                                                                              \
+    L::load(x_lane + size_t(a.nf - 1) * ROWS, cls_);                                                        \
+    const T* pk_ = a.ptab + size_t(uint32_t(__builtin_amdgcn_readlane(int(my_t), j))) * size_t(a.p_stride) + \
+                   size_t(SR_META() & SR_M_INDEX) * size_t(a.n_classes);                                    \
+    _Pragma("unroll") for (int r = 0; r < R; ++r)(o)[r] = pk_[int(cls_[r])];                                \
+  }
+// a parameter as a binary node's operand (as the F variants take a feature): PR op(tos, P), PL op(P, tos)
+#define SR_BCASE_PR(ID, ENABLED)                       \
+  case SR_PBIN_OPC(ID, SR_V_PR): {                     \
+    if constexpr (PARAM) {                             \
+      if (ENABLED) {                                   \
+        T o[R];                                        \
+        SR_PARAM_ROWS(o);                              \
+        SR_BIN_EACH(tos[r], o[r], ID);                 \
+        if constexpr (!sr_untracked_b(ID)) SR_TRACK(); \
+      }                                                \
+    }                                                  \
+    break;                                             \
+  }
+#define SR_BCASE_P(ID, ENABLED)                        \
+  SR_BCASE_PR(ID, ENABLED)                             \
+  case SR_PBIN_OPC(ID, SR_V_PL): {                     \
+    if constexpr (PARAM) {                             \
+      if (ENABLED) {                                   \
+        T o[R];                                        \
+        SR_PARAM_ROWS(o);                              \
+        SR_BIN_EACH(o[r], tos[r], ID);                 \
+        if constexpr (!sr_untracked_b(ID)) SR_TRACK(); \
+      }                                                \
+    }                                                  \
+    break;                                             \
+  }
 // PAIR instructions: op(leaf, leaf) with the first feature in meta, the second feature in c0 (FF)
 // or the constant in the c words (FC / CF); the PUSH forms first store the old tos
 #define SR_PCASE(ID, ENABLED, PV, BODY)                          \
@@ -807,8 +844,14 @@ __device__ __forceinline__ typename SrWindow<T>::type sr_window_lds(const uint4*
 // lane j, the non-finite / suspicious bits in scalar masks.
 // LK: elementwise loss fixed at compile time (SR_LOSS_L2 / SR_LOSS_L1), or -1 = a.loss_kind.
 // VSTK: the operand stack (<= 2 slots: every tree of <= 30 nodes) lives in VGPRs.
-template <typename T, int R, int MODE, bool GATHER, int TIER, int W, int LK, bool VSTK>
-__global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, TIER, W, VSTK, LK, GATHER, MODE>::value)) sr_tile_kernel(const SrEvalArgs<T> a) {
+// TIERP: the operator tier (SR_TIER_BASIC / SR_TIER_FULL), | SR_TIER_PARAM for the builds of parametric
+// calls (ParametricExpression batches), which alone implement LOAD_PARAM and the P binary operands
+// (sr_ops.h).  A flag on this parameter, not a parameter of its own: the kernels of plain calls keep
+// their symbol names and — the new cases are empty in them — their code.
+template <typename T, int R, int MODE, bool GATHER, int TIERP, int W, int LK, bool VSTK>
+__global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_FULL), W, VSTK, LK, GATHER, MODE>::value)) sr_tile_kernel(const SrEvalArgs<T> a) {
+  constexpr int TIER = TIERP & SR_TIER_FULL;
+  constexpr bool PARAM = (TIERP & SR_TIER_PARAM) != 0;
   constexpr int SR_WAVES = W;
   constexpr int SR_BLOCK = W * 64;
   using L = SrLane<T, R>;
@@ -882,8 +925,10 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, TIER, W, VSTK, LK
   const int S = gcount > wave ? (gcount - wave + SR_WAVES - 1) / SR_WAVES : 0;
   const int my_pos = tree0 + wave + SR_WAVES * lane;
   uint32_t my_pb = 0u, my_pe = 0u;
+  uint32_t my_t = 0u;  // PARAM: the caller's index of lane j's tree (its rows of the parameter table)
   if (lane < S) {
     const uint32_t t = a.perm ? a.perm[my_pos] : uint32_t(my_pos);
+    if constexpr (PARAM) my_t = t;
     my_pb = a.offsets[t];
     my_pe = a.ends ? a.ends[t] : a.offsets[t + 1];
   }
@@ -1110,6 +1155,22 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, TIER, W, VSTK, LK
               }
               break;
             }
+            case SR_OP_LOAD_PARAM_PUSH:
+              if constexpr (PARAM) {
+                SR_PUSH_TOS();
+              }
+              [[fallthrough]];
+            case SR_OP_LOAD_PARAM: {
+              // a parameter leaf: checked exactly where a feature leaf is (track_x: the call's leaf bound,
+              // max(max|X|, max|P|), is huge or non-finite)
+              if constexpr (PARAM) {
+                SR_PARAM_ROWS(tos);
+                if (FAST_CHECK && a.track_x && (SR_META() & SR_M_CHECK)) {
+                  SR_TRACK();
+                }
+              }
+              break;
+            }
             case SR_OP_LOAD_DERIVED_PUSH:
               SR_PUSH_TOS();
               [[fallthrough]];
@@ -1165,6 +1226,15 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, TIER, W, VSTK, LK
             SR_BCASE_FULL(SR_B_MOD) SR_BCASE_FULL(SR_B_GREATER) SR_BCASE_FULL(SR_B_LESS)
             SR_BCASE_FULL(SR_B_GREATER_EQUAL) SR_BCASE_FULL(SR_B_LESS_EQUAL) SR_BCASE_FULL(SR_B_COND)
             SR_BCASE_FULL(SR_B_LOGICAL_OR) SR_BCASE_FULL(SR_B_LOGICAL_AND) SR_BCASE_FULL(SR_B_ATAN2)
+            // parameter operands (PARAM builds; empty cases elsewhere)
+            SR_BCASE_PR(SR_B_ADD, true) SR_BCASE_PR(SR_B_MUL, true) SR_BCASE_P(SR_B_SUB, true)
+            SR_BCASE_P(SR_B_DIV, true)
+            SR_BCASE_P(SR_B_POW, TIER == SR_TIER_FULL) SR_BCASE_P(SR_B_MAX, TIER == SR_TIER_FULL)
+            SR_BCASE_P(SR_B_MIN, TIER == SR_TIER_FULL) SR_BCASE_P(SR_B_MOD, TIER == SR_TIER_FULL)
+            SR_BCASE_P(SR_B_GREATER, TIER == SR_TIER_FULL) SR_BCASE_P(SR_B_LESS, TIER == SR_TIER_FULL)
+            SR_BCASE_P(SR_B_GREATER_EQUAL, TIER == SR_TIER_FULL) SR_BCASE_P(SR_B_LESS_EQUAL, TIER == SR_TIER_FULL)
+            SR_BCASE_P(SR_B_COND, TIER == SR_TIER_FULL) SR_BCASE_P(SR_B_LOGICAL_OR, TIER == SR_TIER_FULL)
+            SR_BCASE_P(SR_B_LOGICAL_AND, TIER == SR_TIER_FULL) SR_BCASE_P(SR_B_ATAN2, TIER == SR_TIER_FULL)
             default:
               break;
           }
@@ -1492,6 +1562,17 @@ hipError_t sr_launch_tile(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s) {
   hipLaunchKernelGGL((sr_tile_kernel<T, R, MODE, GATHER, TIER, W, LK, VSTK>), dim3(n_blocks), dim3(W * 64), plan.total, s, a);
   return hipGetLastError();
 }
+// the same for a parametric call: the build flagged SR_TIER_PARAM, the table in the argument block's last
+// fields (a.nf counts the hidden class row: at least 2 staged rows)
+template <typename T, int R, int MODE, bool GATHER, int TIER, int W, int LK, bool VSTK>
+hipError_t sr_launch_tile_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int n_blocks, hipStream_t s) {
+  if (p.ptab == nullptr || p.n_classes < 1 || p.p_stride < 0 || a.nf < 2) return hipErrorInvalidValue;
+  SrEvalArgs<T> b = a;
+  b.ptab = p.ptab;
+  b.p_stride = p.p_stride;
+  b.n_classes = p.n_classes;
+  return sr_launch_tile<T, R, MODE, GATHER, TIER | SR_TIER_PARAM, W, LK, VSTK>(b, n_blocks, s);
+}
 
 // ------------------------------------------------------------------ derived columns
 // Column k = op_k(X[f_k]) over rows [0, n_pad) of the view (gathered rows through row_idx; rows past
@@ -1544,6 +1625,10 @@ hipError_t sr_launch_derived(const T* X, int64_t ld, const int64_t* row_idx, int
 // element type / mode) so the build compiles them in parallel; see the Makefile.
 #define SR_INSTANTIATE_WLV(T, R, MODE, GATHER, TIER, W, LK, VSTK) \
   template hipError_t sr_launch_tile<T, R, MODE, GATHER, TIER, W, LK, VSTK>(const SrEvalArgs<T>&, int, hipStream_t);
+// the builds for parametric calls (sr_inst_*param*.hip; the set sr_launch_eval_param dispatches over)
+#define SR_INSTANTIATE_PARAM(T, R, MODE, GATHER, TIER, W, LK, VSTK) \
+  template hipError_t sr_launch_tile_param<T, R, MODE, GATHER, TIER, W, LK, VSTK>(const SrEvalArgs<T>&, const SrParamArgs<T>&, int, \
+                                                                                  hipStream_t);
 #define SR_INSTANTIATE_WL(T, R, MODE, GATHER, TIER, W, LK) SR_INSTANTIATE_WLV(T, R, MODE, GATHER, TIER, W, LK, false)
 #define SR_INSTANTIATE_W(T, R, MODE, GATHER, TIER, W) SR_INSTANTIATE_WL(T, R, MODE, GATHER, TIER, W, -1)
 #define SR_INSTANTIATE(T, R, MODE, GATHER, TIER) SR_INSTANTIATE_WL(T, R, MODE, GATHER, TIER, 4, -1)

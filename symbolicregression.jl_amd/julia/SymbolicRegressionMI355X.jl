@@ -27,7 +27,8 @@ using SymbolicRegression
 using SymbolicRegression: AbstractOptions, Dataset, LossFunctionsModule, PopulationModule, PopMemberModule,
                           SingleIterationModule, ConstantOptimizationModule
 using DynamicExpressions: AbstractExpressionNode, AbstractExpression, Expression, Node, get_tree, get_operators,
-                          get_scalar_constants, set_scalar_constants!, simplify_tree!, combine_operators
+                          get_scalar_constants, set_scalar_constants!, simplify_tree!, combine_operators,
+                          ParametricExpression, ParametricNode, get_metadata
 
 const LIB = get(ENV, "SR_AMD_LIB", joinpath(@__DIR__, "..", "lib", "libsr_amd.so"))
 
@@ -45,6 +46,15 @@ struct SrTreeBatch
     feature::Ptr{UInt16}
     constant::Ptr{UInt8}
     val::Ptr{Cvoid}
+end
+
+# Mirrors `sr_param_batch`: the parameter side of a batch of ParametricExpression trees.
+struct SrParamBatch
+    is_parameter::Ptr{UInt8}
+    parameter::Ptr{UInt16}
+    max_parameters::Int32
+    n_classes::Int32
+    parameters::Ptr{Cvoid}
 end
 
 last_error() = unsafe_string(ccall((:sr_last_error, LIB), Cstring, ()))
@@ -96,6 +106,19 @@ function device_dataset(ctx::DeviceContext, dataset::Dataset{T}) where {T}
             y = Vector{T}(dataset.y)
             w = dataset.weights === nothing ? nothing : Vector{T}(dataset.weights)
             out = Ref{Ptr{Cvoid}}(C_NULL)
+            # a parametric search's per-row category column (dataset.extra.class, 1-based): uploaded with
+            # the data; plain calls on such a dataset are unaffected
+            cls = dataset_classes(dataset)
+            if cls !== nothing
+                GC.@preserve X y w cls begin
+                    check(ccall((:sr_dataset_upload_classes, LIB), Cint,
+                                (Ptr{Cvoid}, Cint, Ptr{T}, Int64, Int64, Ptr{T}, Ptr{Cvoid}, Ptr{Int32}, Int32,
+                                 Ref{Ptr{Cvoid}}),
+                                ctx.handle, T === Float32 ? SR_DTYPE_F32 : SR_DTYPE_F64, X, size(X, 1), size(X, 2),
+                                y, w === nothing ? C_NULL : Ptr{Cvoid}(pointer(w)), cls, Int32(maximum(cls)), out))
+                end
+                return out[]
+            end
             # every host buffer stays rooted for the whole call (the library copies them)
             GC.@preserve X y w begin
                 check(ccall((:sr_dataset_upload, LIB), Cint,
@@ -108,9 +131,42 @@ function device_dataset(ctx::DeviceContext, dataset::Dataset{T}) where {T}
     end
 end
 
-"""Trees the device evaluates: plain `Expression{T,Node{T,2}}` / `Node` (parametric and template
-expressions keep their own evaluators on the CPU)."""
+"""`dataset.extra.class` as `Vector{Int32}` (ids 1..n_classes), or `nothing`."""
+function dataset_classes(dataset::Dataset)
+    extra = dataset.extra
+    (extra isa NamedTuple && haskey(extra, :class)) || return nothing
+    return Vector{Int32}(extra.class)
+end
+
+"""Trees the device evaluates as plain trees: `Expression{T,Node{T,2}}` / `Node` (template expressions
+keep their own evaluator on the CPU; `ParametricExpression`s take the parametric calls below)."""
 device_tree(t) = t isa Node || (t isa Expression && get_tree(t) isa Node)
+parametric_tree(t) = t isa ParametricExpression && get_tree(t) isa ParametricNode
+
+"""The `sr_param_batch` arrays of `ParametricExpression`s whose nodes `flatten` has laid out: per node
+`is_parameter` / `parameter`, and every `get_metadata(ex).parameters` matrix ((max_parameters, n_classes),
+column-major: exactly the ABI layout) one after another.  `nothing` when the matrices differ in size."""
+function flatten_parameters(trees::AbstractVector, ::Type{T}) where {T}
+    is_parameter = UInt8[]; parameter = UInt16[]; mats = T[]
+    dims = size(get_metadata(first(trees)).parameters)
+    for ex in trees
+        P = get_metadata(ex).parameters
+        size(P) == dims || return nothing
+        append!(mats, vec(Matrix{T}(P)))
+        stack = Any[get_tree(ex)]
+        while !isempty(stack)   # the same pre-order walk as `flatten`
+            n = pop!(stack)
+            isp = n.degree == 0 && n.is_parameter
+            push!(is_parameter, isp ? 0x01 : 0x00)
+            push!(parameter, isp ? n.parameter : 0x0000)
+            if n.degree != 0
+                n.degree == 2 && push!(stack, n.r)
+                push!(stack, n.l)
+            end
+        end
+    end
+    return (; is_parameter, parameter, mats, max_parameters=Int32(dims[1]), n_classes=Int32(dims[2]))
+end
 
 """Pre-order struct-of-arrays of many `Node{T,2}` trees (get_scalar_constants order)."""
 function flatten(trees::AbstractVector, ::Type{T}) where {T}
@@ -144,6 +200,7 @@ caller keeps the reference's CPU path)."""
 function eval_loss_batch(trees::AbstractVector, dataset::Dataset{T,L}, options::AbstractOptions;
                          idx::Union{Nothing,AbstractVector{Int}}=nothing) where {T,L}
     isempty(trees) && return (L[], Bool[])
+    all(parametric_tree, trees) && return eval_loss_batch_parametric(trees, dataset, options; idx=idx)
     all(device_tree, trees) || return nothing
     ctx = context()
     oid = opset_id(ctx, get_operators(first(trees), options))
@@ -165,6 +222,70 @@ function eval_loss_batch(trees::AbstractVector, dataset::Dataset{T,L}, options::
         check(rc)
     end
     return L.(losses), complete .== 0x01
+end
+
+"""The same for `ParametricExpression`s (`LF.eval_tree_dispatch(::ParametricExpression, dataset, options)`,
+src/ParametricExpression.jl:69-100, behind `_eval_loss`): every tree on its own
+`get_metadata(ex).parameters[:, dataset.extra.class]`.  `nothing` (the CPU path) for a dataset without
+classes or matrices of different sizes."""
+function eval_loss_batch_parametric(trees::AbstractVector, dataset::Dataset{T,L}, options::AbstractOptions;
+                                    idx::Union{Nothing,AbstractVector{Int}}=nothing) where {T,L}
+    cls = dataset_classes(dataset)
+    cls === nothing && return nothing
+    ctx = context()
+    oid = opset_id(ctx, get_operators(first(trees), options))
+    lk = loss_kind(options)
+    (oid === nothing || lk === nothing) && return nothing
+    f = flatten(trees, T)
+    p = flatten_parameters(trees, T)
+    (p === nothing || p.n_classes != maximum(cls)) && return nothing
+    losses = Vector{T}(undef, length(trees))
+    complete = Vector{UInt8}(undef, length(trees))
+    rows = idx === nothing ? nothing : Int64.(idx .- 1)
+    dsh = device_dataset(ctx, dataset)
+    GC.@preserve f p rows losses complete begin
+        b = SrTreeBatch(length(trees), pointer(f.offsets), pointer(f.degree), pointer(f.op),
+                        pointer(f.feature), pointer(f.constant), Ptr{Cvoid}(pointer(f.val)))
+        pb = SrParamBatch(pointer(p.is_parameter), pointer(p.parameter), p.max_parameters, p.n_classes,
+                          Ptr{Cvoid}(pointer(p.mats)))
+        rc = ccall((:sr_eval_loss_batch_parametric, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{SrTreeBatch}, Ref{SrParamBatch}, Ptr{Int64}, Int64, Cint, Ptr{T},
+                    Ptr{UInt8}),
+                   ctx.handle, dsh, oid, b, pb, rows === nothing ? C_NULL : pointer(rows),
+                   rows === nothing ? 0 : length(rows), lk, losses, complete)
+        rc == SR_ERR_UNSUPPORTED_OP && return nothing
+        check(rc)
+    end
+    return L.(losses), complete .== 0x01
+end
+
+"""Batched `eval_tree_array` of `ParametricExpression`s on `dataset` (its X and classes):
+(predictions::Matrix{T} [n, n_trees], complete::Vector{Bool}), or `nothing` as above."""
+function eval_tree_array_parametric(trees::AbstractVector, dataset::Dataset{T}, options::AbstractOptions) where {T}
+    cls = dataset_classes(dataset)
+    (cls === nothing || isempty(trees)) && return nothing
+    ctx = context()
+    oid = opset_id(ctx, get_operators(first(trees), options))
+    oid === nothing && return nothing
+    f = flatten(trees, T)
+    p = flatten_parameters(trees, T)
+    (p === nothing || p.n_classes != maximum(cls)) && return nothing
+    pred = Matrix{T}(undef, dataset.n, length(trees))
+    complete = Vector{UInt8}(undef, length(trees))
+    dsh = device_dataset(ctx, dataset)
+    GC.@preserve f p pred complete begin
+        b = SrTreeBatch(length(trees), pointer(f.offsets), pointer(f.degree), pointer(f.op),
+                        pointer(f.feature), pointer(f.constant), Ptr{Cvoid}(pointer(f.val)))
+        pb = SrParamBatch(pointer(p.is_parameter), pointer(p.parameter), p.max_parameters, p.n_classes,
+                          Ptr{Cvoid}(pointer(p.mats)))
+        rc = ccall((:sr_eval_tree_array_parametric, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{SrTreeBatch}, Ref{SrParamBatch}, Ptr{Int64}, Int64, Ptr{T},
+                    Ptr{UInt8}),
+                   ctx.handle, dsh, oid, b, pb, C_NULL, 0, pred, complete)
+        rc == SR_ERR_UNSUPPORTED_OP && return nothing
+        check(rc)
+    end
+    return pred, complete .== 0x01
 end
 
 # Options.elementwise_loss -> (SrLossKind, parameter) (include/sr_amd.h SR_LOSS_*; LossFunctions.jl types as

@@ -28,6 +28,7 @@ from .loss import (
 from .mutation import gen_random_batch, gen_random_population, gen_random_tree_fixed_size, make_random_leaf
 from .node import (
     Node,
+    ParametricExpression,
     TreeBatch,
     apply_binary,
     apply_unary,
@@ -39,7 +40,7 @@ from .node import (
     string_tree,
 )
 from .operators import OperatorEnum
-from .options import Options
+from .options import Options, ParametricExpressionSpec
 from .search import HallOfFame, PopMember, SearchOptions, equation_search
 
 __all__ = [
@@ -50,5 +51,5 @@ __all__ = [
     "update_baseline_loss_", "score_func", "compute_complexity", "gen_random_tree_fixed_size",
     "gen_random_population", "gen_random_batch", "make_random_leaf", "get_context", "device_available", "DeviceContext",
     "SRError", "UnsupportedOperatorError", "optimize_constants_batch", "equation_search", "SearchOptions",
-    "PopMember", "HallOfFame",
+    "PopMember", "HallOfFame", "ParametricExpression", "ParametricExpressionSpec",
 ]

@@ -92,6 +92,11 @@ EXPORTED_SYMBOLS = (
     "sr_optimize_constants_batch",
     "sr_gen_random_population",
     "sr_optimize_constants_callbacks",
+    "sr_dataset_upload_classes",
+    "sr_eval_loss_batch_parametric",
+    "sr_eval_loss_batch_views_parametric",
+    "sr_eval_tree_array_parametric",
+    "sr_compile_info_parametric",
 )
 
 # mutation kinds in sr_search_options.mutation_weights order (SR_MUT_*)
@@ -122,6 +127,16 @@ class SrTreeBatch(ctypes.Structure):
         ("feature", POINTER(c_uint16)),
         ("constant", POINTER(c_uint8)),
         ("val", c_void_p),
+    ]
+
+
+class SrParamBatch(ctypes.Structure):
+    _fields_ = [
+        ("is_parameter", POINTER(c_uint8)),
+        ("parameter", POINTER(c_uint16)),
+        ("max_parameters", ctypes.c_int32),
+        ("n_classes", ctypes.c_int32),
+        ("parameters", c_void_p),
     ]
 
 
@@ -180,6 +195,7 @@ def _load():
         ),
         "sr_register_loss": (c_int, [P, c_int, c_double, POINTER(c_int)]),
         "sr_dataset_upload": (c_int, [P, c_int, P, c_int64, c_int64, P, P, POINTER(P)]),
+        "sr_dataset_upload_classes": (c_int, [P, c_int, P, c_int64, c_int64, P, P, P, ctypes.c_int32, POINTER(P)]),
         "sr_dataset_free": (c_int, [P]),
         "sr_dataset_info": (c_int, [P, POINTER(c_int), POINTER(c_int64), POINTER(c_int64)]),
         "sr_eval_loss_batch": (
@@ -195,6 +211,23 @@ def _load():
             [P, P, c_int, POINTER(SrTreeBatch), P, c_int, P, c_int64, c_int, P, P, P],
         ),
         "sr_eval_tree_array": (c_int, [P, P, c_int, POINTER(SrTreeBatch), P, c_int64, P, P]),
+        "sr_eval_loss_batch_parametric": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int64, c_int, P, P],
+        ),
+        "sr_eval_loss_batch_views_parametric": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int, P, c_int64, c_int, P, P],
+        ),
+        "sr_eval_tree_array_parametric": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int64, P, P],
+        ),
+        "sr_compile_info_parametric": (
+            c_int,
+            [c_int, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), POINTER(SrParamBatch),
+             c_int64, c_int64, P, P, POINTER(c_int), P, c_int64],
+        ),
         "sr_eval_loss_partials": (
             c_int,
             [P, P, c_int, POINTER(SrTreeBatch), c_int64, c_int, P, P, c_int],

@@ -3,6 +3,10 @@
 ``X`` is ``[nfeatures, n]`` exactly as in Julia.  The device copy is uploaded once per context
 (transposed to per-feature contiguous rows on the GPU) and stays resident; minibatches
 (``SubDataset``) only send their row indices.
+
+``extra={"class": ...}`` is the per-row category column of a parametric search
+(``dataset.extra.class``, src/ParametricExpression.jl:69-100): Julia's ids, integers in
+``1..n_classes``; the device keeps it next to ``X`` for ``ParametricExpression`` scoring.
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ from .device import get_context
 
 
 class Dataset:
-    def __init__(self, X, y=None, *, weights=None, variable_names=None, loss_type=None):
+    def __init__(self, X, y=None, *, weights=None, variable_names=None, loss_type=None, extra=None, n_classes=None):
         X = np.asarray(X)
         if X.ndim != 2:
             raise ValueError("X must be a [nfeatures, n] matrix")
@@ -47,7 +51,32 @@ class Dataset:
         self.use_baseline = True
         self.baseline_loss = X.dtype.type(1.0)
         self.variable_names = variable_names or [f"x{i + 1}" for i in range(self.nfeatures)]
+        self.extra = dict(extra) if extra else {}
+        self.n_classes = 0
+        if "class" in self.extra:
+            cls = np.asarray(self.extra["class"])
+            if cls.shape != (self.n,):
+                raise ValueError(f"extra['class'] must have n = {self.n} entries, got shape {cls.shape}")
+            if not np.issubdtype(cls.dtype, np.integer):
+                if not np.all(cls == np.floor(cls)):
+                    raise ValueError("extra['class'] must hold integer class ids")
+            cls = cls.astype(np.int64)
+            if cls.min() < 1:
+                raise ValueError(f"extra['class'] holds class {int(cls.min())}: ids are 1..n_classes")
+            self.n_classes = int(cls.max()) if n_classes is None else int(n_classes)
+            if cls.max() > self.n_classes:
+                raise ValueError(f"extra['class'] holds class {int(cls.max())} above n_classes = {self.n_classes}")
+            if self.n_classes >= 1 << 24:
+                raise ValueError("n_classes must stay below 2^24")
+            self.extra["class"] = np.ascontiguousarray(cls, dtype=np.int32)
+        elif n_classes is not None:
+            raise ValueError("n_classes needs extra={'class': ...}")
         self._device = {}
+
+    @property
+    def classes(self):
+        """The rows' class ids (1-based), or None."""
+        return self.extra.get("class")
 
     # ---------------------------------------------------------------- device residency
     def device_handle(self, ctx=None):
@@ -59,18 +88,21 @@ class Dataset:
             y = None if self.y is None else np.ascontiguousarray(self.y)
             w = None if self.weights is None else np.ascontiguousarray(self.weights)
             out = ctypes.c_void_p()
-            _lib.check(
-                _lib.lib.sr_dataset_upload(
-                    ctx.handle,
-                    _lib.SR_DTYPE_F32 if self.dtype == np.float32 else _lib.SR_DTYPE_F64,
-                    Xj.ctypes.data_as(ctypes.c_void_p),
-                    self.nfeatures,
-                    self.n,
-                    None if y is None else y.ctypes.data_as(ctypes.c_void_p),
-                    None if w is None else w.ctypes.data_as(ctypes.c_void_p),
-                    ctypes.byref(out),
-                )
+            args = (
+                ctx.handle,
+                _lib.SR_DTYPE_F32 if self.dtype == np.float32 else _lib.SR_DTYPE_F64,
+                Xj.ctypes.data_as(ctypes.c_void_p),
+                self.nfeatures,
+                self.n,
+                None if y is None else y.ctypes.data_as(ctypes.c_void_p),
+                None if w is None else w.ctypes.data_as(ctypes.c_void_p),
             )
+            if self.n_classes:
+                cls = self.extra["class"]
+                _lib.check(_lib.lib.sr_dataset_upload_classes(*args, cls.ctypes.data_as(ctypes.c_void_p),
+                                                              self.n_classes, ctypes.byref(out)))
+            else:
+                _lib.check(_lib.lib.sr_dataset_upload(*args, ctypes.byref(out)))
             h = out
             self._device[key] = h
         return h
@@ -134,6 +166,11 @@ class SubDataset:
     @property
     def n(self) -> int:
         return int(self._indices.size)
+
+    @property
+    def classes(self):
+        c = self._dataset.classes
+        return None if c is None else c[self._indices]
 
     def is_weighted(self) -> bool:
         return self._dataset.weights is not None

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .dataset import Dataset, SubDataset
 from .device import get_context
-from .node import Node, TreeBatch, flatten_trees
+from .node import Node, ParametricExpression, TreeBatch, flatten_trees
 
 
 def _as_batch(trees, dtype) -> TreeBatch:
@@ -24,6 +24,20 @@ def _as_batch(trees, dtype) -> TreeBatch:
     if isinstance(trees, Node) or hasattr(trees, "tree"):
         trees = [trees]
     return flatten_trees(trees, dtype=dtype)
+
+
+def _param_struct(tb: TreeBatch, full, options):
+    """The ``sr_param_batch`` of a parametric batch, checked against the dataset's classes and the
+    options' ``ParametricExpressionSpec`` (the library checks them again)."""
+    if not full.n_classes:
+        raise ValueError("ParametricExpression trees need a dataset with extra={'class': ...}")
+    if tb.parameters.shape[2] != full.n_classes:
+        raise ValueError(f"parameters have {tb.parameters.shape[2]} class columns, the dataset {full.n_classes} classes")
+    spec = getattr(options, "expression_spec", None)
+    if spec is not None and tb.parameters.shape[1] != spec.max_parameters:
+        raise ValueError(f"parameters have {tb.parameters.shape[1]} rows, expression_spec max_parameters = "
+                         f"{spec.max_parameters}")
+    return tb.to_param_struct()
 
 
 def eval_loss_batch(trees, dataset, options, *, ctx=None):
@@ -45,6 +59,13 @@ def eval_loss_batch(trees, dataset, options, *, ctx=None):
         raise ValueError("dataset has no y")
     idx = dataset.indices
     s = tb.to_struct()
+    if tb.parametric:  # ParametricExpression trees: the same call with the batch's parameter side
+        ps = _param_struct(tb, full, options)
+        _lib.check(_lib.lib.sr_eval_loss_batch_parametric(
+            ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), ctypes.byref(ps),
+            None if idx is None else idx.ctypes.data_as(ctypes.c_void_p), 0 if idx is None else int(idx.size),
+            ctx.loss_code(options), losses.ctypes.data_as(ctypes.c_void_p), complete.ctypes.data_as(ctypes.c_void_p)))
+        return losses, complete.astype(bool)
     _lib.check(
         _lib.lib.sr_eval_loss_batch(
             ctx.handle,
@@ -81,6 +102,12 @@ def eval_loss_batch_views(trees, dataset, options, tree_view, view_rows, *, ctx=
     complete = np.empty(nt, dtype=np.uint8)
     s = tb.to_struct()
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    if tb.parametric:
+        ps = _param_struct(tb, full, options)
+        _lib.check(_lib.lib.sr_eval_loss_batch_views_parametric(
+            ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), ctypes.byref(ps),
+            p(tv), int(vr.shape[0]), p(vr), int(vr.shape[1]), ctx.loss_code(options), p(losses), p(complete)))
+        return losses, complete.astype(bool)
     _lib.check(_lib.lib.sr_eval_loss_batch_views(
         ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), p(tv), int(vr.shape[0]),
         p(vr), int(vr.shape[1]), ctx.loss_code(options), p(losses), p(complete)))
@@ -92,6 +119,8 @@ def eval_grad_batch_views(trees, dataset, options, tree_view, view_rows, *, ctx=
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
+    if tb.parametric:
+        raise NotImplementedError("gradients of ParametricExpression trees are not on the device path")
     nt = tb.n_trees
     tv, vr = _views(tree_view, view_rows, nt)
     losses = np.empty(nt, dtype=full.dtype)
@@ -120,6 +149,8 @@ def eval_grad_batch(trees, dataset, options, *, ctx=None):
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
+    if tb.parametric:
+        raise NotImplementedError("gradients of ParametricExpression trees are not on the device path")
     nt = tb.n_trees
     losses = np.empty(nt, dtype=full.dtype)
     complete = np.empty(nt, dtype=np.uint8)
@@ -153,6 +184,13 @@ def eval_tree_array_batch(trees, dataset, options, *, ctx=None):
     out = np.empty((tb.n_trees, n_rows), dtype=full.dtype)
     complete = np.empty(tb.n_trees, dtype=np.uint8)
     s = tb.to_struct()
+    if tb.parametric:
+        ps = _param_struct(tb, full, options)
+        _lib.check(_lib.lib.sr_eval_tree_array_parametric(
+            ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), ctypes.byref(ps),
+            None if idx is None else idx.ctypes.data_as(ctypes.c_void_p), 0 if idx is None else int(idx.size),
+            out.ctypes.data_as(ctypes.c_void_p), complete.ctypes.data_as(ctypes.c_void_p)))
+        return out, complete.astype(bool)
     _lib.check(
         _lib.lib.sr_eval_tree_array(
             ctx.handle,
@@ -168,13 +206,28 @@ def eval_tree_array_batch(trees, dataset, options, *, ctx=None):
     return out, complete.astype(bool)
 
 
-def eval_tree_array(tree, X, options):
+def eval_tree_array(tree, X, *args, options=None):
     """``eval_tree_array(tree, X, options) -> (output, complete)``
-    (src/InterfaceDynamicExpressions.jl:58-88).  ``X`` is ``[nfeatures, n]`` or a Dataset."""
+    (src/InterfaceDynamicExpressions.jl:58-88).  ``X`` is ``[nfeatures, n]`` or a Dataset.
+    A ``ParametricExpression`` takes the rows' classes as well: ``eval_tree_array(ex, X, classes, options)``
+    (1-based ids; with a Dataset that has classes, ``eval_tree_array(ex, dataset, options)``)."""
+    if options is not None:
+        args = args + (options,)
+    if len(args) not in (1, 2):
+        raise TypeError("eval_tree_array(tree, X, options) or eval_tree_array(ex, X, classes, options)")
+    options = args[-1]
+    classes = args[0] if len(args) == 2 else None
     if isinstance(X, (Dataset, SubDataset)):
+        if classes is not None:
+            raise TypeError("a Dataset carries its own classes (extra={'class': ...})")
         out, comp = eval_tree_array_batch([tree], X, options)
         return out[0], bool(comp[0])
-    ds = Dataset(np.asarray(X))
+    if classes is not None:
+        if not isinstance(tree, ParametricExpression):
+            raise TypeError("classes are for ParametricExpression trees")
+        ds = Dataset(np.asarray(X), extra={"class": classes}, n_classes=tree.n_classes)
+    else:
+        ds = Dataset(np.asarray(X))
     try:
         out, comp = eval_tree_array_batch([tree], ds, options)
     finally:
@@ -200,7 +253,9 @@ def eval_loss(tree, dataset, options, *, regularization: bool = True, idx=None):
 
 def compute_complexity(tree, options=None) -> int:
     """Default complexity = number of nodes (src/Complexity.jl:29-41)."""
-    t = getattr(tree, "tree", tree)
+    t = tree
+    while not isinstance(t, Node) and hasattr(t, "tree"):  # PopMember -> (ParametricExpression ->) Node
+        t = t.tree
     return t.count_nodes()
 
 
@@ -216,7 +271,7 @@ def loss_to_cost(loss, use_baseline: bool, baseline, member, options, complexity
 
 def eval_cost(dataset, member, options, *, complexity=None):
     """``eval_cost`` (src/LossFunctions.jl:193-209) -> (cost, loss)."""
-    tree = getattr(member, "tree", member)
+    tree = member if isinstance(member, ParametricExpression) else getattr(member, "tree", member)
     result_loss = eval_loss(tree, dataset, options)
     cost = loss_to_cost(result_loss, dataset.use_baseline, dataset.baseline_loss, member, options, complexity)
     return cost, result_loss
@@ -224,7 +279,7 @@ def eval_cost(dataset, member, options, *, complexity=None):
 
 def eval_cost_batch(members: Sequence, dataset, options, *, complexities=None):
     """Batched ``eval_cost`` for a population: one device launch for all members."""
-    trees = [getattr(m, "tree", m) for m in members]
+    trees = [m if isinstance(m, ParametricExpression) else getattr(m, "tree", m) for m in members]
     losses, _ = eval_loss_batch(trees, dataset, options)
     if complexities is None:
         complexities = [compute_complexity(t) for t in trees]

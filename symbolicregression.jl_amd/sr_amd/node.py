@@ -4,6 +4,11 @@ Fields follow DE 2.x: ``degree`` (0 leaf / 1 unary / 2 binary), ``constant``, ``
 (1-based), ``op`` (1-based index into ``options.operators.ops[degree]``), children ``l``/``r``.
 ``flatten_trees`` produces the struct-of-arrays ``sr_tree_batch`` the C ABI takes (pre-order =
 ``get_scalar_constants`` order, test/integration/ad/zygote/test_derivatives.jl:127-155).
+
+``ParametricExpression`` (src/ParametricExpression.jl) adds DE's ``ParametricNode`` fields: a leaf with
+``is_parameter`` reads ``parameters[parameter, class[row]]`` of its expression's own
+``(max_parameters, n_classes)`` matrix; ``flatten_trees`` of such expressions also yields the
+``sr_param_batch`` arrays (a batch is all plain or all parametric).
 """
 from __future__ import annotations
 
@@ -18,10 +23,13 @@ from .operators import OperatorEnum, canonical_binary, canonical_unary, print_na
 
 
 class Node:
-    __slots__ = ("degree", "constant", "val", "feature", "op", "l", "r")
+    __slots__ = ("degree", "constant", "val", "feature", "op", "l", "r", "is_parameter", "parameter")
 
-    def __init__(self, *args, val=None, feature=None, op=None, l=None, r=None, children=None):
+    def __init__(self, *args, val=None, feature=None, op=None, l=None, r=None, children=None, parameter=None):
         # Node("x3") / Node(feature=3) / Node(val=1.5) / Node(op=1, l=..) / Node(op=2, l=.., r=..)
+        # Node("p2") / Node(parameter=2): a ParametricNode's parameter leaf
+        self.is_parameter = False
+        self.parameter = 0
         self.degree = 0
         self.constant = False
         self.val = 0.0
@@ -32,9 +40,12 @@ class Node:
         if args:
             if len(args) == 1 and isinstance(args[0], str):
                 s = args[0]
-                if not s.startswith("x"):
-                    raise ValueError(f"variable names must look like 'x1', got {s!r}")
-                feature = int(s[1:])
+                if s.startswith("p") and s[1:].isdigit():
+                    parameter = int(s[1:])
+                elif not s.startswith("x"):
+                    raise ValueError(f"variable names must look like 'x1' (parameters 'p1'), got {s!r}")
+                else:
+                    feature = int(s[1:])
             elif isinstance(args[0], int) and len(args) in (2, 3):
                 op = args[0]
                 children = args[1:]
@@ -53,18 +64,24 @@ class Node:
             self.l = l
             self.r = r
             self.degree = 2 if r is not None else 1
+        elif parameter is not None:
+            if int(parameter) < 1:
+                raise ValueError("parameters are numbered from 1")
+            self.is_parameter = True
+            self.parameter = int(parameter)
         elif feature is not None:
             self.feature = int(feature)
         elif val is not None:
             self.constant = True
             self.val = val
         else:
-            raise ValueError("Node needs val=, feature= or op=")
+            raise ValueError("Node needs val=, feature=, parameter= or op=")
 
     # ------------------------------------------------------------------ DE-style utilities
     def copy(self) -> "Node":
         n = Node.__new__(Node)
         n.degree, n.constant, n.val, n.feature, n.op = self.degree, self.constant, self.val, self.feature, self.op
+        n.is_parameter, n.parameter = self.is_parameter, self.parameter
         n.l = self.l.copy() if self.l is not None else None
         n.r = self.r.copy() if self.r is not None else None
         return n
@@ -73,6 +90,7 @@ class Node:
         """DE ``set_node!``: overwrite this node's contents with ``other``'s."""
         self.degree, self.constant, self.val, self.feature, self.op = (
             other.degree, other.constant, other.val, other.feature, other.op)
+        self.is_parameter, self.parameter = other.is_parameter, other.parameter
         self.l, self.r = other.l, other.r
 
     def preorder(self) -> List["Node"]:
@@ -180,6 +198,8 @@ def string_tree(tree: Node, operators: Optional[OperatorEnum] = None) -> str:
 
     def rec(n: Node) -> str:
         if n.degree == 0:
+            if n.is_parameter:
+                return f"p{n.parameter}"
             return repr(n.val) if n.constant else f"x{n.feature}"
         if n.degree == 1:
             return f"{name(1, n.op)}({rec(n.l)})"
@@ -233,11 +253,43 @@ def parse_expression(expr: str, operators) -> Node:
     return rec(ast.parse(expr, mode="eval"))
 
 
+class ParametricExpression:
+    """``ParametricExpression(tree, parameters)``: a tree whose ``p_k`` leaves read
+    ``parameters[k - 1, class - 1]`` per row (``parameters``: ``[max_parameters, n_classes]``, the layout
+    of ``get_metadata(ex).parameters``)."""
+
+    def __init__(self, tree: "Node", parameters):
+        self.tree = tree
+        self.parameters = np.asarray(parameters)
+        if self.parameters.ndim != 2:
+            raise ValueError("parameters must be a [max_parameters, n_classes] matrix")
+        kmax = max((n.parameter for n in tree.preorder() if n.degree == 0 and n.is_parameter), default=0)
+        if kmax > self.parameters.shape[0]:
+            raise ValueError(f"tree uses p{kmax} but parameters has {self.parameters.shape[0]} rows")
+
+    @property
+    def max_parameters(self) -> int:
+        return int(self.parameters.shape[0])
+
+    @property
+    def n_classes(self) -> int:
+        return int(self.parameters.shape[1])
+
+    def copy(self) -> "ParametricExpression":
+        return ParametricExpression(self.tree.copy(), self.parameters.copy())
+
+    def __repr__(self):
+        return f"ParametricExpression({string_tree(self.tree)}, parameters={self.parameters.tolist()})"
+
+
 # ------------------------------------------------------------------ flattening for the C ABI
 class TreeBatch:
-    """Pre-order struct-of-arrays of many trees, kept alive while the C call runs."""
+    """Pre-order struct-of-arrays of many trees, kept alive while the C call runs.  A parametric batch
+    also holds ``is_parameter`` / ``parameter`` per node and ``parameters[n_trees, max_parameters,
+    n_classes]`` (the ``sr_param_batch`` arrays); a plain batch has ``is_parameter = None``."""
 
-    def __init__(self, offsets, degree, op, feature, constant, val):
+    def __init__(self, offsets, degree, op, feature, constant, val, is_parameter=None, parameter=None,
+                 parameters=None):
         self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         self.degree = np.ascontiguousarray(degree, dtype=np.uint8)
         self.op = np.ascontiguousarray(op, dtype=np.uint8)
@@ -245,6 +297,40 @@ class TreeBatch:
         self.constant = np.ascontiguousarray(constant, dtype=np.uint8)
         self.val = np.ascontiguousarray(val)
         self.n_trees = len(self.offsets) - 1
+        self.is_parameter = self.parameter = self.parameters = None
+        if is_parameter is not None:
+            self.is_parameter = np.ascontiguousarray(is_parameter, dtype=np.uint8)
+            self.parameter = np.ascontiguousarray(parameter, dtype=np.uint16)
+            self.parameters = np.ascontiguousarray(parameters, dtype=self.val.dtype)
+            if self.parameters.ndim != 3 or self.parameters.shape[0] != self.n_trees:
+                raise ValueError("parameters must be [n_trees, max_parameters, n_classes]")
+            if self.is_parameter.shape != self.degree.shape or self.parameter.shape != self.degree.shape:
+                raise ValueError("is_parameter / parameter must have one entry per node")
+
+    @property
+    def parametric(self) -> bool:
+        return self.is_parameter is not None
+
+    def _sel(self, offs, nodes, trees, val=None) -> "TreeBatch":
+        """The batch of the given nodes / trees (index arrays or slices), parameter side included."""
+        p = self.parametric
+        return TreeBatch(offs, self.degree[nodes], self.op[nodes], self.feature[nodes], self.constant[nodes],
+                         self.val[nodes] if val is None else val, self.is_parameter[nodes] if p else None,
+                         self.parameter[nodes] if p else None, self.parameters[trees] if p else None)
+
+    def to_param_struct(self) -> "_lib.SrParamBatch":
+        """The ``sr_param_batch`` of a parametric batch (keep the returned struct alive during the call)."""
+        if not self.parametric:
+            raise ValueError("not a parametric batch")
+        s = _lib.SrParamBatch()
+        # each tree's matrix in Julia's column-major (max_parameters, n_classes) layout
+        self._params_jl = np.ascontiguousarray(self.parameters.transpose(0, 2, 1))
+        s.is_parameter = self.is_parameter.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        s.parameter = self.parameter.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))
+        s.max_parameters = int(self.parameters.shape[1])
+        s.n_classes = int(self.parameters.shape[2])
+        s.parameters = self._params_jl.ctypes.data_as(ctypes.c_void_p)
+        return s
 
     @property
     def n_nodes(self) -> int:
@@ -255,7 +341,9 @@ class TreeBatch:
         return int(np.count_nonzero(self.degree))
 
     def astype(self, dtype) -> "TreeBatch":
-        return TreeBatch(self.offsets, self.degree, self.op, self.feature, self.constant, self.val.astype(dtype))
+        return TreeBatch(self.offsets, self.degree, self.op, self.feature, self.constant, self.val.astype(dtype),
+                         self.is_parameter, self.parameter,
+                         self.parameters.astype(dtype) if self.parametric else None)
 
     def tree_sizes(self) -> np.ndarray:
         return np.diff(self.offsets)
@@ -266,8 +354,7 @@ class TreeBatch:
         b, e = self.offsets[idx], self.offsets[idx + 1]
         nodes = np.concatenate([np.arange(x, y) for x, y in zip(b, e)]) if idx.size else np.zeros(0, np.int64)
         offs = np.concatenate([[0], np.cumsum(e - b)])
-        return TreeBatch(offs, self.degree[nodes], self.op[nodes], self.feature[nodes], self.constant[nodes],
-                         self.val[nodes])
+        return self._sel(offs, nodes, idx)
 
     def to_struct(self) -> _lib.SrTreeBatch:
         def ptr(a, t):
@@ -300,14 +387,14 @@ class TreeBatch:
         """Same trees with their constants replaced (set_scalar_constants! for the whole batch)."""
         val = self.val.copy()
         val[self.constant_mask()] = np.asarray(consts, dtype=val.dtype)
-        return TreeBatch(self.offsets, self.degree, self.op, self.feature, self.constant, val)
+        return self._sel(self.offsets, slice(None), slice(None), val)
 
     def subset(self, idx) -> "TreeBatch":
         idx = np.asarray(idx, dtype=np.int64)
         starts, ends = self.offsets[idx], self.offsets[idx + 1]
         sel = np.concatenate([np.arange(s, e) for s, e in zip(starts, ends)]) if len(idx) else np.zeros(0, np.int64)
         offs = np.concatenate([[0], np.cumsum(ends - starts)])
-        return TreeBatch(offs, self.degree[sel], self.op[sel], self.feature[sel], self.constant[sel], self.val[sel])
+        return self._sel(offs, sel, idx)
 
     def tree(self, k: int) -> Node:
         b, e = int(self.offsets[k]), int(self.offsets[k + 1])
@@ -318,6 +405,8 @@ class TreeBatch:
             pos[0] += 1
             d = int(self.degree[i])
             if d == 0:
+                if self.parametric and self.is_parameter[i]:
+                    return Node(parameter=int(self.parameter[i]))
                 if self.constant[i]:
                     return Node(val=self.val[i].item())
                 return Node(feature=int(self.feature[i]))
@@ -327,18 +416,35 @@ class TreeBatch:
 
         t = rec()
         assert pos[0] == e
-        return t
+        return ParametricExpression(t, self.parameters[k].copy()) if self.parametric else t
 
 
 def flatten_trees(trees: Iterable[Node], dtype=np.float32) -> TreeBatch:
-    nodes, offsets = [], [0]
+    nodes, offsets, mats = [], [0], []
+    n_items = 0
     for t in trees:
+        n_items += 1
+        if isinstance(getattr(t, "tree", None), ParametricExpression):  # a PopMember holding one
+            t = t.tree
+        if isinstance(t, ParametricExpression):
+            mats.append(t.parameters)
         t = getattr(t, "tree", t)  # PopMember / Expression wrappers
         nodes.extend(t.preorder())
         offsets.append(len(nodes))
+    if mats and len(mats) != n_items:
+        raise ValueError("a batch is either all plain trees or all ParametricExpressions")
+    if not mats and any(n.degree == 0 and n.is_parameter for n in nodes):
+        raise ValueError("a tree with parameter leaves needs its ParametricExpression (its parameters)")
+    if mats and len({m.shape for m in mats}) != 1:
+        raise ValueError("every ParametricExpression of a batch needs the same (max_parameters, n_classes)")
     degree = [n.degree for n in nodes]
     op = [n.op for n in nodes]
     feature = [n.feature for n in nodes]
     constant = [1 if (n.degree == 0 and n.constant) else 0 for n in nodes]
     val = [n.val if n.constant else 0.0 for n in nodes]
+    if mats:
+        isp = [1 if (n.degree == 0 and n.is_parameter) else 0 for n in nodes]
+        par = [n.parameter if (n.degree == 0 and n.is_parameter) else 0 for n in nodes]
+        return TreeBatch(offsets, degree, op, feature, constant, np.array(val, dtype=dtype), isp, par,
+                         np.stack(mats).astype(dtype))
     return TreeBatch(offsets, degree, op, feature, constant, np.array(val, dtype=dtype))

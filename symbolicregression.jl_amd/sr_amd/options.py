@@ -52,6 +52,19 @@ def parse_loss(spec):
     return kind, float(arg)
 
 
+class ParametricExpressionSpec:
+    """``ParametricExpressionSpec(max_parameters=...)`` (src/ParametricExpression.jl): expressions are
+    ``ParametricExpression``s with ``p1..p<max_parameters>`` leaves, one parameter column per class."""
+
+    def __init__(self, *, max_parameters: int):
+        if int(max_parameters) < 1:
+            raise ValueError("max_parameters must be positive")
+        self.max_parameters = int(max_parameters)
+
+    def __repr__(self):
+        return f"ParametricExpressionSpec(max_parameters={self.max_parameters})"
+
+
 class Options:
     def __init__(
         self,
@@ -83,6 +96,7 @@ class Options:
         device: str = "mi355x",
         deterministic: bool = False,
         seed=None,
+        expression_spec=None,
     ):
         self.operators = operators if operators is not None else OperatorEnum(unary_operators, binary_operators)
         if callable(elementwise_loss) and not isinstance(elementwise_loss, str):
@@ -120,6 +134,11 @@ class Options:
         self.device = "mi355x"
         self.deterministic = deterministic
         self.seed = seed
+        # None (plain Expression{T,Node{T,2}}) or a ParametricExpressionSpec; the scoring calls take either
+        # kind of tree whatever the spec says, the spec bounds a parametric tree's parameter indices
+        if expression_spec is not None and not isinstance(expression_spec, ParametricExpressionSpec):
+            raise ValueError("expression_spec: only ParametricExpressionSpec is supported by the device path")
+        self.expression_spec = expression_spec
 
     @property
     def nops(self):
