@@ -519,7 +519,9 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * is the reference's in-order fold in T of its elementwise losses (src/LossFunctions.jl:38-58), divided
  * in T; 0: the f64 sum of rounds 1-5, whose last bits — ~5e-4 relative at 2^20 rows in Float32 —
  * differ), "fold_store_mb" / "fold_slot_mb" (the fold's stored-loss and slow-segment budgets),
- * "fold_delta_log2" (the fold plan's window), "fold_seg_max" (the longest row block folded: a folding
+ * "fold_single_pass" (1, the default: a path-2 call's loss launch composes each row block's fold steps
+ * under candidate binades, and the FOLD pass runs only the blocks they do not cover; 0: the FOLD
+ * pass runs every block of every complete tree), "fold_delta_log2" (the fold plan's window), "fold_seg_max" (the longest row block folded: a folding
  * call takes enough row blocks for it), "fold_rows_max" (the longest fold, 2^24 rows: a longer call —
  * C4's 2^26 rows — keeps the f64 sum, as "ref_fold" 0).  Results do not depend on any knob but these
  * three ("ref_fold", "fold_seg_max", "fold_rows_max": whether a call folds) and — without the fold only
@@ -542,6 +544,11 @@ int sr_tuning_info(sr_ctx* ctx, int* used_derived_columns, int64_t* exact_trees)
  * window and were folded through the prediction pass instead, and the fold launches' device time (ms,
  * HIP events; 0 with "timing" off). */
 int sr_ref_fold_info(sr_ctx* ctx, int* path, int64_t* n_folded, int64_t* n_fallback, double* fold_kernel_ms);
+/* The last path-2 call's (tree, row block) pairs (each output may be NULL): `taken`, whose composed step
+ * the plan took from the loss launch's candidate binades (tuning "fold_single_pass", 1 by default: plain
+ * single-GPU Float32 calls of the BASIC tier over the full view), and `rerun`, which the FOLD-mode pass
+ * ran.  Both 0 after any other call.  Waits for the call's device work. */
+int sr_last_fold_cand(sr_ctx* ctx, int64_t* taken, int64_t* rerun);
 
 #ifdef __cplusplus
 }

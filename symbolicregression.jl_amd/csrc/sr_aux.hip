@@ -605,12 +605,18 @@ struct SrStoredRows {
 };
 
 // Large calls: one wave per launch position; codes [rb][np] (slots of the FOLD mode's slow segments
-// from the call's counter; past slot_cap a slow segment gets SKIP, which fails its tree in the walk).
+// from the call's counter; past slot_cap a slow segment gets SKIP, which fails its tree in the walk — a
+// tree whose FIRST segment finds no slot gets a steps code there, which fails it in the walk as well,
+// and SKIP everywhere else, so it takes the fallback and is counted instead of keeping the f64 sum).
+// cand (NULL: none): the loss launch's candidates (sr_fold_dev.h, SR_TIER_CAND builds).  A steps block
+// whose binade is one of its candidates, without a tie there, takes its pair from them: the pair
+// goes to ft.tab, the code stays q for the walk, and ft.sq = SR_FSQ_TAKEN keeps the FOLD pass off the
+// block.  slot_next[1] / [2] count the call's (tree, block) pairs taken so / left to the FOLD pass.
 template <typename T>
 __global__ void __launch_bounds__(256) sr_fold_plan_kernel(const double* __restrict__ part, int np, int n_rb,
                                                            const uint32_t* __restrict__ perm, SrFoldWho who,
                                                            double delta, SrFoldTabs ft, int* __restrict__ slot_next,
-                                                           int slot_cap) {
+                                                           int slot_cap, const int4* __restrict__ cand) {
   const int lane = int(threadIdx.x) & 63;
   const int p = int(blockIdx.x) * 4 + int(threadIdx.x) / 64;
   if (p >= np) return;  // wave-uniform
@@ -648,6 +654,8 @@ __global__ void __launch_bounds__(256) sr_fold_plan_kernel(const double* __restr
                                                                                : double(who.n_terms) * 1.4901161193847656e-08);
     if (mx <= mn * (1.0 + 0.0078125) && delta < wide) delta = wide;
   }
+  bool lost = false;  // (wave-uniform: the tree's first segment found no slot)
+  int n_taken = 0, n_rerun = 0;
   for (int c0 = 0; c0 < n_rb; c0 += 64) {
     const int rb = c0 + lane;
     const bool in = rb < n_rb;
@@ -676,12 +684,37 @@ __global__ void __launch_bounds__(256) sr_fold_plan_kernel(const double* __restr
       if (lane == 0) base = atomicAdd(slot_next, __popcll(sm));
       base = __shfl(base, 0, 64);
       const int k = base + __popcll(sm & ((uint64_t(1) << lane) - 1u));
-      if (slow) cd = k < slot_cap ? SR_FCODE_SLOT0 + k : SR_FCODE_SKIP;
+      const bool first = rb == 0 && who.first;
+      if (slow) cd = k < slot_cap ? SR_FCODE_SLOT0 + k : (first ? cd : SR_FCODE_SKIP);
+      if (__builtin_amdgcn_ballot_w64(slow && first && k >= slot_cap)) lost = true;
     }
+    if (lost && !(c0 == 0 && lane == 0)) {
+      cd = SR_FCODE_SKIP;
+      sqv = SR_FCODE_SKIP;
+    }
+    // a steps block: its pair from the loss launch's candidates when its binade is among them
+    bool taken = false;
+    if (cand && in && !lost && cd != SR_FCODE_SKIP && cd < SR_FCODE_SLOT0) {
+      const int4 c = cand[size_t(rb) * size_t(np) + size_t(p)];
+      const int64_t k = c.x == SR_FCODE_SKIP ? -1 : int64_t(cd) - int64_t(c.x);
+      const int32_t tv = k == 0 ? c.y : (k == 1 ? c.z : (k == 2 ? c.w : SR_FCAND_TIE));
+      if (tv >= 0) {
+        taken = true;
+        sqv = SR_FSQ_TAKEN;
+        static_cast<typename SrFoldTab<T>::Pair*>(ft.tab)[size_t(rb) * size_t(np) + size_t(p)] =
+            SrFoldTab<T>::pair(typename SrFoldTab<T>::I(tv), typename SrFoldTab<T>::I(tv));
+      }
+    }
+    n_taken += __popcll(__builtin_amdgcn_ballot_w64(taken));
+    n_rerun += __popcll(__builtin_amdgcn_ballot_w64(in && !lost && !taken && cd != SR_FCODE_SKIP));
     if (in) {
       ft.code[size_t(rb) * size_t(np) + size_t(p)] = cd;
       ft.sq[size_t(rb) * size_t(np) + size_t(p)] = sqv;
     }
+  }
+  if (lane == 0) {
+    if (n_taken) atomicAdd(slot_next + 1, n_taken);
+    if (n_rerun) atomicAdd(slot_next + 2, n_rerun);
   }
 }
 
@@ -1237,10 +1270,11 @@ __global__ void __launch_bounds__(64) sr_fold_walk_kernel(SrFoldTabs ft, SrFoldW
 
 template <typename T>
 hipError_t sr_launch_fold_plan(const double* part, int np, int n_rb, const uint32_t* perm, const SrFoldWho& who,
-                               double delta, SrFoldTabs ft, int* slot_next, int slot_cap, hipStream_t s) {
+                               double delta, SrFoldTabs ft, int* slot_next, int slot_cap, const int4* cand,
+                               hipStream_t s) {
   if (np <= 0) return hipSuccess;
   hipLaunchKernelGGL(sr_fold_plan_kernel<T>, dim3(unsigned((np + 3) / 4)), dim3(256), 0, s, part, np, n_rb, perm, who,
-                     delta, ft, slot_next, slot_cap);
+                     delta, ft, slot_next, slot_cap, cand);
   return hipGetLastError();
 }
 template <typename T>
@@ -1273,7 +1307,7 @@ hipError_t sr_launch_fold_walk(SrFoldTabs ft, const SrFoldWho& who, int np, int 
 }
 #define SR_INSTANTIATE_FOLD2(T)                                                                                      \
   template hipError_t sr_launch_fold_plan<T>(const double*, int, int, const uint32_t*, const SrFoldWho&, double,   \
-                                             SrFoldTabs, int*, int, hipStream_t);                                      \
+                                             SrFoldTabs, int*, int, const int4*, hipStream_t);                        \
   template hipError_t sr_launch_fold_stab<T>(const double*, int, int, int64_t, int64_t, const uint32_t*,              \
                                              const SrFoldWho&, double, const T*, SrFoldTabs, const uint32_t*,          \
                                              const uint8_t*, double*, uint32_t*, hipStream_t);                         \
@@ -1391,6 +1425,20 @@ int sr_vstk_rows(int elem_size, int64_t n_rows, int requested) {
   if (requested == 4 || requested == 8) return 0;
   return n_rows >= (int64_t(1) << 17) ? SR_VSTK_DEFAULT_ROWS : 0;
 }
+
+template <typename T>
+hipError_t sr_launch_loss_cand(const SrEvalArgs<T>& a, int R, int waves, int n_blocks, hipStream_t s) {
+  if constexpr (sizeof(T) == 4) {  // (sr_inst_f32_cand.hip)
+    if (R != 16 || waves != 4 || a.fold_cand == nullptr) return hipErrorInvalidValue;
+    return a.loss_kind == SR_LOSS_L2
+               ? sr_launch_tile<T, 16, SR_MODE_LOSS, false, SR_TIER_BASIC | SR_TIER_CAND, 4, SR_LOSS_L2, true>(a, n_blocks, s)
+               : sr_launch_tile<T, 16, SR_MODE_LOSS, false, SR_TIER_BASIC | SR_TIER_CAND, 4, -1, true>(a, n_blocks, s);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+template hipError_t sr_launch_loss_cand<float>(const SrEvalArgs<float>&, int, int, int, hipStream_t);
+template hipError_t sr_launch_loss_cand<double>(const SrEvalArgs<double>&, int, int, int, hipStream_t);
 
 template <typename T>
 hipError_t sr_launch_eval(const SrEvalArgs<T>& a, int mode, bool gather, int tier, int R, int waves, bool vstk,

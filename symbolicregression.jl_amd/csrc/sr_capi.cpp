@@ -316,8 +316,17 @@ struct sr_ctx {
   int64_t fold_seg_max = 16384;  // SR_AMD_FOLD_SEG_MAX: calls whose row blocks are longer keep the f64 sum
   int64_t fold_rows_max = int64_t(1) << 24;  // SR_AMD_FOLD_ROWS_MAX: longer folds keep the f64 sum
   int fold_debug_fail = 0;   // (tests: "fold_debug_fail")
-  int fold_reduce = 1;
-  int fold_pre_start = 1;    // SR_AMD_FOLD_PRE_START: stored-loss folds start in the pair kernel (0: in the walk)       // SR_AMD_FOLD_REDUCE: stored-loss folds reduce in the pair kernel (0: a reduce launch)
+  int fold_reduce = 1;       // SR_AMD_FOLD_REDUCE: stored-loss folds reduce in the pair kernel (0: a reduce launch)
+  int fold_pre_start = 1;    // SR_AMD_FOLD_PRE_START: stored-loss folds start in the pair kernel (0: in the walk)
+  // SR_AMD_FOLD_SINGLE_PASS / "fold_single_pass": the loss launch of a FOLD-mode call (path 2) composes each
+  // row block's steps under candidate binades, and the plan takes the blocks whose binade is among
+  // them, so the FOLD pass runs only what is left (0: every block of every complete tree again).  Plain
+  // single-GPU Float32 BASIC calls over the full view, register-stack launch; every other call keeps the
+  // two passes.
+  int fold_single_pass = 1;
+  DevBuf fold_cand;          // the candidates, [row block][position] int4 (sr_fold_dev.h)
+  bool fold_cand_read = true;  // fold_ctl's counters of the last call are in n_cand_* below
+  int64_t n_cand_taken_last = 0, n_cand_rerun_last = 0;
   int fold_walk_dbg = 0;     // SR_AMD_FOLD_WALK_DBG (analysis): 2 no O(1) slow blocks, 4 no serial start
   int fold_stats = 0;        // SR_AMD_FOLD_STATS=1: per-tree walk statistics to stderr after each call (analysis)
   DevBuf fold_dbg;
@@ -604,7 +613,7 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
     return SR_OK;
   }
   SR_HIP_CHECK(sr_launch_fold_plan<T>(part, np, nrb, fr.a.perm, who, job.delta, ft, ctx->fold_ctl.as<int>(),
-                                      job.slot_cap, cs));
+                                      job.slot_cap, fr.a.fold_cand, cs));
   SrEvalArgs<T> fa = fr.a;
   fa.hint = nullptr;
   fa.out_sum = nullptr;
@@ -618,6 +627,7 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
   fa.fold_loss = ctx->fold_store.as<T>();
   fa.fold_slot_rows = job.slot_rows;
   fa.fold_pos_stride = 0;
+  fa.fold_cand = nullptr;
   if (fr.p.ptab)  // (a parametric call's launches: the PARAM builds)
     SR_HIP_CHECK(sr_launch_eval_param<T>(fa, fr.p, SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, int(fr.n_blocks), cs));
   else
@@ -821,7 +831,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
   //  the choice below depends on the largest shard's rows, known to every rank)
   const int64_t fold_n_terms = shard ? ((ds->w && ds->shard_w_min < 0.0) ? 0 : n_total) : fold_terms(ds, n_eval);
   int fold_path = 0;
-  int64_t fold_slot_rows = 0;
+  int64_t fold_slot_rows = 0, fold_slots = 0;
   if (shard) ctx->fold_job.reset();
   if (ctx->want_fold && ctx->ref_fold && mode == SR_MODE_LOSS && nt > 0 && fold_n_terms > 0) {
     // rows a position's store covers under either kernel's grid (row blocks x rows: >= the view)
@@ -861,12 +871,15 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       SR_HIP_CHECK(ctx->fold_store.ensure(size_t(nt) * size_t(pos_rows) * sizeof(T)));
     } else if (sizeof(T) == 4 && fold_mode_builds) {
       fold_path = 2;
-      // (slots for ~24 slow segments per tree — C2 averages 10 — up to fold_slot_mb)
-      const int64_t slots = std::max<int64_t>(1, std::min<int64_t>(int64_t(nt) * 24, ctx->fold_slot_mb * 1048576 /
-                                                                                     (fold_slot_rows * int64_t(sizeof(T)))));
+      // (slots for ~24 slow segments per tree — C2 averages 10; a handful of trees over many row blocks
+      //  can need more each: at least 1,024 — up to fold_slot_mb, which caps the call's slots whatever an
+      //  earlier call left allocated: the buffer only ever grows)
+      fold_slots = std::max<int64_t>(1, ctx->fold_slot_mb * 1048576 / (fold_slot_rows * int64_t(sizeof(T))));
+      const int64_t slots = std::min<int64_t>(std::max<int64_t>(int64_t(nt) * 24, 1024), fold_slots);
       SR_HIP_CHECK(ctx->fold_store.ensure(size_t(slots) * size_t(fold_slot_rows) * sizeof(T)));
       SR_HIP_CHECK(ctx->fold_ctl.ensure(64));
-      SR_HIP_CHECK(hipMemsetAsync(ctx->fold_ctl.p, 0, sizeof(int), s));  // the call's slot counter
+      // the call's slot counter, and its (tree, block) pairs taken from the candidates / left to the FOLD pass
+      SR_HIP_CHECK(hipMemsetAsync(ctx->fold_ctl.p, 0, 4 * sizeof(int), s));
     }
     if (fold_path && ctx->fold_stats) {
       SR_HIP_CHECK(ctx->fold_dbg.ensure(size_t(nt) * sizeof(int4) + 16));
@@ -879,9 +892,15 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       SR_HIP_CHECK(ctx->fold_tab2.ensure(n_part * sizeof(typename SrFoldTab<T>::Pair) + 16));
     }
   }
+  // the candidate-composing loss launch (sr_ctx::fold_single_pass): plain calls only
+  const bool fold_cand = fold_path == 2 && ctx->fold_single_pass && sizeof(T) == 4 && tier == SR_TIER_BASIC &&
+                         !gather && !multi && !shard && ctx->param == nullptr && n_rb > 1;
+  if (fold_cand) SR_HIP_CHECK(ctx->fold_cand.ensure(n_part * sizeof(int4) + 16));
   if (!ctx->internal_pass) {  // (the fallback's prediction passes leave the call's record alone)
     ctx->fold_path_last = fold_path;
     ctx->fold_timed_last = false;
+    ctx->fold_cand_read = fold_path != 2;
+    ctx->n_cand_taken_last = ctx->n_cand_rerun_last = 0;
   }
   // {Σ loss | flags | the fold's values | their status}, one allocation (one DMA back)
   ctx->outs_flag_off = align256(size_t(nt) * sizeof(double) + 8);
@@ -1048,8 +1067,8 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
   // stored losses on one GPU: the pair kernel reduces the partials itself (one launch fewer a call;
   // SR_AMD_FOLD_REDUCE=0: the reduce launch)
   fjob.fuse_reduce = fold_path == 1 && !shard && mode == SR_MODE_LOSS && ctx->fold_reduce;
-  fjob.slot_cap = fold_path == 2 ? int(std::min<int64_t>(INT_MAX / 2, int64_t(ctx->fold_store.cap /
-                                                                             (size_t(fold_slot_rows) * sizeof(T)))))
+  fjob.slot_cap = fold_path == 2 ? int(std::min<int64_t>({int64_t(INT_MAX / 2), fold_slots,
+                                                          int64_t(ctx->fold_store.cap / (size_t(fold_slot_rows) * sizeof(T)))}))
                                  : 0;
   size_t fold_store_at = 0;  // (stored losses: the regions one after another, [position][n_rb x rb rows])
   char* const outs_base = (host_out || fold_mirror) ? ctx->h_outs.as<char>() : ctx->outs.as<char>();
@@ -1399,8 +1418,14 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       SR_HIP_CHECK(hipMemsetAsync(ctx->stamps.p, 0, size_t(ctx->n_stamps) * sizeof(uint64_t), cs));
       a.stamps = ctx->stamps.as<uint64_t>();
 #endif
+      // (the register-stack launch at 16 rows per lane has the candidate build; the LDS-stack launch's few
+      //  deep trees take the whole FOLD pass)
+      const bool cand_launch = fold_cand && vstk && Rc == 16 && g.W == 4 && g.n_row_blocks > 1;
+      if (cand_launch) a.fold_cand = ctx->fold_cand.as<int4>() + size_t(n_rb) * size_t(t0 + p0);
       if (parametric)
         SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
+      else if (cand_launch)
+        SR_HIP_CHECK(sr_launch_loss_cand<T>(a, Rc, g.W, int(n_blocks), cs));
       else
         SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
       if (fold_path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g});
@@ -3727,6 +3752,7 @@ int sr_init(int device, sr_ctx** out) {
   if (const char* v = std::getenv("SR_AMD_FOLD_WALK_DBG")) ctx->fold_walk_dbg = std::atoi(v) & 6;
   if (const char* v = std::getenv("SR_AMD_FOLD_REDUCE")) ctx->fold_reduce = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_PRE_START")) ctx->fold_pre_start = std::atoi(v) != 0 ? 1 : 0;
+  if (const char* v = std::getenv("SR_AMD_FOLD_SINGLE_PASS")) ctx->fold_single_pass = std::atoi(v) != 0 ? 1 : 0;
   hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e == hipSuccess && std::getenv("SR_AMD_EAGER_STREAM2")) e = ctx->need_stream2();  // (A/B: the round-4 layout)
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming);
@@ -3773,7 +3799,7 @@ int sr_shutdown(sr_ctx* ctx) {
                       &ctx->hint, &ctx->jsum_prog, &ctx->jsum_scratch, &ctx->probe_sum, &ctx->probe_flag, &ctx->g_code, &ctx->g_offsets, &ctx->g_consts, &ctx->g_const_off,
                       &ctx->g_items, &ctx->g_part, &ctx->g_out, &ctx->derived_cols, &ctx->probe_derived, &ctx->coll_buf, &ctx->coll_packed, &ctx->ctl, &ctx->fold_io, &ctx->group_cnt,
                       &ctx->fold_code, &ctx->fold_tab, &ctx->fold_store, &ctx->fold_ctl, &ctx->fold_io2, &ctx->fold_sq,
-                      &ctx->fold_tab2, &ctx->ptab})
+                      &ctx->fold_tab2, &ctx->ptab, &ctx->fold_cand})
       b->release();
     for (HostBuf* b : {&ctx->h_prog, &ctx->h_outs, &ctx->h_grad, &ctx->h_coll, &ctx->h_part, &ctx->h_exact, &ctx->h_ptab})
       b->release();
@@ -4567,6 +4593,10 @@ int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value) {
     ctx->fold_slot_mb = value < 1 ? 1 : value;
     return SR_OK;
   }
+  if (std::strcmp(name, "fold_single_pass") == 0) {  // candidate binades in the loss launch (SR_AMD_FOLD_SINGLE_PASS)
+    ctx->fold_single_pass = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
   if (std::strcmp(name, "fold_debug_fail") == 0) {  // tests: trees t % value == 0 take the fold's fallback
     ctx->fold_debug_fail = int(value < 0 ? 0 : value);
     return SR_OK;
@@ -4671,6 +4701,23 @@ int sr_ref_fold_info(sr_ctx* ctx, int* path, int64_t* n_folded, int64_t* n_fallb
   if (n_folded) *n_folded = ctx->n_ref_ok_last;
   if (n_fallback) *n_fallback = ctx->n_ref_fail_last;
   if (fold_kernel_ms) *fold_kernel_ms = ctx->fold_kernel_ms_last;
+  return SR_OK;
+}
+
+int sr_last_fold_cand(sr_ctx* ctx, int64_t* taken, int64_t* rerun) {
+  if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
+  Lock l(ctx);
+  if (!ctx->fold_cand_read) {  // (the plan's counters of the last FOLD-mode call, read once)
+    int h[4] = {0, 0, 0, 0};
+    SR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->stream2) SR_HIP_CHECK(hipStreamSynchronize(ctx->stream2));
+    SR_HIP_CHECK(hipMemcpy(h, ctx->fold_ctl.p, sizeof(h), hipMemcpyDeviceToHost));
+    ctx->n_cand_taken_last = h[1];
+    ctx->n_cand_rerun_last = h[2];
+    ctx->fold_cand_read = true;
+  }
+  if (taken) *taken = ctx->n_cand_taken_last;
+  if (rerun) *rerun = ctx->n_cand_rerun_last;
   return SR_OK;
 }
 

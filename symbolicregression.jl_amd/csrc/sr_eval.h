@@ -21,6 +21,9 @@ enum { SR_MODE_LOSS = 0, SR_MODE_PRED = 1, SR_MODE_EXACT = 2, SR_MODE_FOLD = 3 }
 enum { SR_TIER_BASIC = 0, SR_TIER_FULL = 1 };
 // a flag on the tile kernel's tier template argument: the build for parametric calls (sr_tile_impl.h)
 enum { SR_TIER_PARAM = 2 };
+// another flag there: the loss build that also composes each row block's in-order fold steps under
+// candidate binades (SrEvalArgs::fold_cand; Float32, BASIC, register stack, 16 rows per lane only)
+enum { SR_TIER_CAND = 4 };
 
 // One row view's launch positions in a several-view launch (sr_eval_loss_batch_views): positions
 // [pos0, pos0 + n_pos) in tree groups of trees_per_block, blocks [block0, block0 + groups x row blocks),
@@ -176,6 +179,11 @@ struct SrEvalArgs {
   const T* ptab;
   int p_stride;
   int n_classes;
+  // SR_TIER_CAND loss builds (last: every other kernel's argument offsets stay as they were):
+  // [n_row_blocks][n_trees] per position, {q0, the block's step under q0, q0 + 1, q0 + 2} (sr_fold_dev.h);
+  // the plan takes a steps block's pair from here when its binade is one of them, and the FOLD pass then
+  // skips the block
+  int4* fold_cand;
 };
 // A parametric call's table: ptab[tree * p_stride + k * n_classes + class] at the caller's tree index (as
 // `offsets`).  The rows' 0-based classes are the last staged X row (the dataset's hidden row:
@@ -207,6 +215,11 @@ int sr_vstk_rows(int elem_size, int64_t n_rows, int requested);
 template <typename T>
 hipError_t sr_launch_eval(const SrEvalArgs<T>& a, int mode, bool gather, int tier, int R, int waves, bool vstk,
                           int n_blocks, hipStream_t s);
+// The candidate-composing loss launch of a large plain call under the in-order fold (SR_TIER_CAND:
+// Float32, BASIC tier, full view, register stack at 16 rows per lane, 4 waves; a.fold_cand set);
+// hipErrorInvalidValue for any other shape.
+template <typename T>
+hipError_t sr_launch_loss_cand(const SrEvalArgs<T>& a, int R, int waves, int n_blocks, hipStream_t s);
 // The same over the kernels built for parametric calls (LOAD_PARAM / P operands; sr_inst_*param*.hip), a
 // smaller set: Float32 BASIC loss at 8 rows per lane (classic, full view or gathered) and 16 (register
 // stack), Float64 at 4 and 8, the FULL tier at 4 / 2, PRED, EXACT with 4 waves (FULL-tier build) and the
@@ -334,7 +347,8 @@ struct SrFoldTabs {
 };
 template <typename T>
 hipError_t sr_launch_fold_plan(const double* part, int np, int n_rb, const uint32_t* perm, const SrFoldWho& who,
-                               double delta, SrFoldTabs ft, int* slot_next, int slot_cap, hipStream_t s);
+                               double delta, SrFoldTabs ft, int* slot_next, int slot_cap, const int4* cand,
+                               hipStream_t s);
 template <typename T>
 hipError_t sr_launch_fold_stab(const double* part, int np, int n_rb, int64_t rb_rows, int64_t n, const uint32_t* perm,
                                const SrFoldWho& who, double delta, const T* losses, SrFoldTabs ft,

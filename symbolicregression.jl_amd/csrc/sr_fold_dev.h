@@ -26,6 +26,21 @@
 //   otherwise            the binade spacing exponent q of the segment's composed step (fold_tab)
 constexpr int32_t SR_FCODE_SKIP = int32_t(0x80000000u);
 constexpr int32_t SR_FCODE_SLOT0 = 0x40000000;
+// A steps block whose pair the plan took from the loss launch's candidates (below): the value of its
+// fold_sq entry (otherwise a slow block's lower window binade, or SKIP).  The walk reads fold_sq of slow
+// blocks only and still sees the block's code q; the FOLD pass does not run the block.
+constexpr int32_t SR_FSQ_TAKEN = 0x7fffffff;
+// The loss launch's candidates of one (row block, position), SR_TIER_CAND builds: x = the lowest
+// candidate binade q0 (SKIP: none — the first row block, a tree found dead), y / z / w = the block's
+// composed step under q0 / q0 + 1 / q0 + 2 when that candidate was composed and no tile of the block has
+// an exact half-ulp tie under it (the pair is then (t, t), bit for bit the FOLD pass's), else
+// SR_FCAND_TIE.  SR_FCAND_N adjacent binades are composed: the two nearest the guess g of the running
+// sum at the block (its first tile's sum times the tiles before the block), q0 = the binade of g / sqrt 2
+// — g in the lower half of its binade (in log scale) takes that binade and the one below, g in the upper
+// half that binade and the one above.  (Three — q^ - 1, q^, q^ + 1 around g's binade — took 78.7 % of
+// C2's blocks against 78.1 % and cost 40 % more in the loss epilogue: DESIGN §12.)
+constexpr int32_t SR_FCAND_TIE = -1;
+constexpr int SR_FCAND_N = 2;
 // per-tree status of the walk (sr_fold_walk_kernel): not folded / the fold's exact value / the plan's
 // speculated binades missed (the host folds that tree through the prediction pass instead)
 enum { SR_FST_NONE = 0, SR_FST_OK = 1, SR_FST_FAIL = 2 };
@@ -238,12 +253,85 @@ struct SrFoldWho {
   }
 };
 
+// The fast path of a tile's composed step (sr_fold_tile_step below), shared with the loss launch's
+// candidate binades (sr_tile_impl.h, SR_TIER_CAND) so that both give the same pairs bit for bit: the
+// tile's steps under the NC adjacent spacings 2^q0, 2^(q0 + 1), ... when no loss of the tile is an exact
+// half ulp of the binade: every step is then rint(l 2^-q) whatever the parity, and the tile's step is
+// their sum (partial sums of integers exact below 2^(mant+1) and monotone above, +Inf included, so a sum
+// that leaves the binade still reads as one, whatever the order of the adds).  ok[c]: no tie under
+// binade c (else t[c] means nothing); t[c]: the tile's step, the same from either parity, saturated at CAP.
+// Float32: two rows per packed instruction; the coarser binades' values are halvings of the finest's
+// (exact but for an underflow, which only ever hides a fraction below 1/2, and for an overflow of the
+// finest, past which every coarser step is past CAP as well), one v_max3 per row pair for max |v - rint v|
+// (a NaN there — Inf - Inf, a step past the type's range — is ignored).
+template <typename T, int R, int NC>
+__device__ __forceinline__ void sr_fold_tile_fast_n(const T (&l)[R], int q0, typename SrFoldTab<T>::I (&t)[NC],
+                                                    bool (&ok)[NC]) {
+  using I = typename SrFoldTab<T>::I;
+  constexpr I CAP = I(1) << (SrFoldTraits<T>::mant + 3);
+  T tsum[NC], dmax[NC];
+  if constexpr (sizeof(T) == 4 && R % 2 == 0) {
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    v2f ts[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      ts[c] = v2f{0.f, 0.f};
+      dmax[c] = T(0);
+    }
+#pragma unroll
+    for (int r = 0; r < R; r += 2) {
+      v2f v = v2f{ldexpf(float(l[r]), -q0), ldexpf(float(l[r + 1]), -q0)};
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        if (c > 0) v = v * 0.5f;
+        const v2f s = v2f{rintf(v.x), rintf(v.y)};
+        const v2f d = v - s;
+        float m;
+        asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(m) : "v"(float(dmax[c])), "v"(d.x), "v"(d.y));
+        dmax[c] = T(m);
+        ts[c] += s;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) tsum[c] = T(ts[c].x + ts[c].y);
+  } else {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      tsum[c] = T(0);
+      dmax[c] = T(0);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const T v = sizeof(T) == 4 ? T(ldexpf(float(l[r]), -(q0 + c))) : T(ldexp(double(l[r]), -(q0 + c)));
+        const T s = sizeof(T) == 4 ? T(rintf(float(v))) : T(rint(double(v)));
+        const T d = v - s;
+        const T ad = d < T(0) ? -d : d;
+        dmax[c] = ad > dmax[c] ? ad : dmax[c];
+        tsum[c] += s;  // (no clamp: a sum past 2^(mant+1) reads as CAP below whatever it is)
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    ok[c] = __builtin_amdgcn_ballot_w64(dmax[c] == T(0.5)) == 0;
+    // wave sum of nonnegative integer values (lane 63's inclusive scan); also on a tie, which is rare:
+    // under a branch the compiler sinks the row sums into it and keeps every rint alive until then
+    const T v = sr_fold_lane(sr_fold_scan(tsum[c]), 63);
+    t[c] = v < T(CAP) ? I(v) : CAP;
+  }
+}
+template <typename T, int R>
+__device__ __forceinline__ bool sr_fold_tile_fast(const T (&l)[R], int q, typename SrFoldTab<T>::I& t) {
+  typename SrFoldTab<T>::I tt[1] = {0};
+  bool ok[1];
+  sr_fold_tile_fast_n<T, R, 1>(l, q, tt, ok);
+  t = tt[0];
+  return ok[0];
+}
+
 // The composed step of one tree over one row tile under binade spacing 2^q: l[R] = the lane's losses
 // in the tile layout (chunk c of lane l = tile rows c*64*C + l*C + j, sr_tile_impl.h SrLane), rows past
-// the view already 0.  Returns the wave-uniform pair (from an even / an odd start).  Fast path: no loss
-// of the tile is an exact half ulp of the binade, so every step is rint(l 2^-q) whatever the parity and
-// the tile's step is their sum (partial sums of integers exact below 2^(mant+1) and monotone above, +Inf
-// included, so a sum that leaves the binade still reads as one); otherwise the ordered
+// the view already 0.  Returns the wave-uniform pair (from an even / an odd start).  Fast path
+// (sr_fold_tile_fast): no loss of the tile is an exact half ulp of the binade; otherwise the ordered
 // composition, row by row in the lane, then over the lanes (lane order = row order in a chunk), then
 // over the chunks.
 template <typename T, int R, int C>
@@ -251,23 +339,8 @@ __device__ __forceinline__ void sr_fold_tile_step(const T (&l)[R], int q, int la
                                                   typename SrFoldTab<T>::I& t1) {
   using I = typename SrFoldTab<T>::I;
   constexpr I CAP = I(1) << (SrFoldTraits<T>::mant + 3);
-  T tsum = T(0), dmax = T(0);
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const T v = sizeof(T) == 4 ? T(ldexpf(float(l[r]), -q)) : T(ldexp(double(l[r]), -q));
-    const T s = sizeof(T) == 4 ? T(rintf(float(v))) : T(rint(double(v)));
-    const T d = v - s;
-    const T ad = d < T(0) ? -d : d;
-    dmax = ad > dmax ? ad : dmax;  // (NaN — a step past the type's range, Inf - Inf — ignored)
-    tsum += s;  // (no clamp: a sum past 2^(mant+1) reads as CAP below whatever it is, +Inf included)
-  }
-  if (__builtin_amdgcn_ballot_w64(dmax == T(0.5)) == 0) {
-    // wave sum of nonnegative integer values (lane 63's inclusive scan): exact below 2^(mant+1), and any
-    // sum past that fails a run the same way
-    const T v = sr_fold_lane(sr_fold_scan(tsum), 63);
-    const I t = v < T(CAP) ? I(v) : CAP;
-    t0 = t;
-    t1 = t;
+  if (sr_fold_tile_fast<T, R>(l, q, t0)) {
+    t1 = t0;
     return;
   }
   I y0 = 0, y1 = 0;  // the tile so far (uniform)

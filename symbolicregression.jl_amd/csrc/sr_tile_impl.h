@@ -852,6 +852,11 @@ template <typename T, int R, int MODE, bool GATHER, int TIERP, int W, int LK, bo
 __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_FULL), W, VSTK, LK, GATHER, MODE>::value)) sr_tile_kernel(const SrEvalArgs<T> a) {
   constexpr int TIER = TIERP & SR_TIER_FULL;
   constexpr bool PARAM = (TIERP & SR_TIER_PARAM) != 0;
+  // the loss launch of a large call under the in-order fold: each row block's composed steps under
+  // candidate binades beside the partials (the epilogue below; SrEvalArgs::fold_cand)
+  constexpr bool CAND = (TIERP & SR_TIER_CAND) != 0;
+  static_assert(!CAND || (MODE == SR_MODE_LOSS && sizeof(T) == 4 && TIER == SR_TIER_BASIC && !GATHER && !PARAM),
+                "candidate binades: the plain Float32 BASIC loss build only");
   constexpr int SR_WAVES = W;
   constexpr int SR_BLOCK = W * 64;
   using L = SrLane<T, R>;
@@ -932,6 +937,19 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
     my_pb = a.offsets[t];
     my_pe = a.ends ? a.ends[t] : a.offsets[t + 1];
   }
+  // FOLD: this row block's plan code of each of the wave's trees (lane j: tree j); SKIP trees are not run,
+  // nor are the steps blocks whose pair the plan took from the loss launch's candidates (SR_FSQ_TAKEN)
+  int32_t my_code = SR_FCODE_SKIP, my_sq = SR_FCODE_SKIP;  // (my_sq: a slow segment's lower window binade)
+  if (MODE == SR_MODE_FOLD) {
+    if (lane < S) {
+      my_code = a.fold_code[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)];
+      if (a.fold_sq) my_sq = a.fold_sq[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)];
+      if (my_sq == SR_FSQ_TAKEN) my_code = SR_FCODE_SKIP;
+      if (my_code < SR_FCODE_SLOT0) my_sq = SR_FCODE_SKIP;
+    }
+    // a workgroup none of whose waves has a tree to run on this row block stages nothing
+    if (!__syncthreads_or(lane < S && my_pe > my_pb && my_code != SR_FCODE_SKIP)) return;
+  }
   // LDS program cache (LOSS): the group's programs are one contiguous span of the launch-ordered code
   // (first position's start .. last position's end); copied once, read by every tile's windows
   const uint4* lcode = reinterpret_cast<const uint4*>(sr_smem + plan.code);
@@ -952,17 +970,16 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
       }
     }
   }
-  // FOLD: this row block's plan code of each of the wave's trees (lane j: tree j); SKIP trees are not run
-  int32_t my_code = SR_FCODE_SKIP, my_sq = SR_FCODE_SKIP;  // (my_sq: a slow segment's lower window binade)
-  if (MODE == SR_MODE_FOLD && lane < S) {
-    my_code = a.fold_code[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)];
-    if (my_code >= SR_FCODE_SLOT0 && a.fold_sq) my_sq = a.fold_sq[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)];
-  }
   const uint64_t live = sr_ballot(lane < S && my_pe > my_pb &&  // empty program: statically incomplete
                                   (MODE != SR_MODE_FOLD || my_code != SR_FCODE_SKIP));
   // FOLD: lane j's tree's composed steps over this row block (a slow segment's: under my_sq, and under
   // my_sq + 1 in facc2 / facc3)
   typename SrFoldTab<T>::I facc0 = 0, facc1 = 0, facc2 = 0, facc3 = 0;
+  // CAND: lane j's tree's lowest candidate binade q0 on this row block (from its first tile's sum) and the
+  // block's steps so far under q0, q0 + 1, ... (SR_FCAND_TIE once a tile has a tie under that binade)
+  int32_t cand_q = SR_FCODE_SKIP;
+  int32_t cand[3] = {0, 0, SR_FCAND_TIE};
+  static_assert(SR_FCAND_N >= 1 && SR_FCAND_N <= 3, "the candidates of a block are one int4");
   uint64_t dmask = 0u, bmask = 0u, emask = 0u;
   double accv = 0.0;
   // dead-tree hints shared across row blocks (LOSS mode): a tree found non-finite by any block is
@@ -1359,6 +1376,12 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
             // (small calls under the in-order fold: every live tree's losses, the fold's tables are
             //  composed from them; a tree found dead later leaves garbage the fold never reads)
             if (a.fold_loss) L::store(a.fold_loss + size_t(tree0 + g) * size_t(a.fold_pos_stride) + size_t(row0) + lane * C, l);
+            // (CAND: the losses whole until the candidates are composed; the reduction below overwrites l)
+            T lc[CAND ? R : 1];
+            if constexpr (CAND) {
+#pragma unroll
+              for (int r = 0; r < R; ++r) lc[r] = l[r];
+            }
             // pairwise over the lane's rows by halves (rows r and r + h: adjacent pairs of rows add as
             // one packed instruction, R - 1 adds in R / 2 instructions); the wave sum follows.  The
             // first level's sums are sums of TWO losses: one of them +Inf means an elementwise loss,
@@ -1414,6 +1437,37 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
               // a loss or a pair sum is +Inf (the reference's fold is then +Inf); otherwise only the
               // longer sums overflowed and the host decides the fold (sr_fold.h)
               if (!(s <= SrM<T>::big) && sr_ballot(pair_max == T(INFINITY))) emask |= bit;
+              if constexpr (CAND) {
+                // The in-order fold's steps of this tile under SR_FCAND_N candidate binades (the FOLD pass's
+                // fast path, sr_fold_tile_fast_n: the same pairs bit for bit), so that the plan can take the
+                // block's pair from here instead of running the tree again.  The running sum's binade at
+                // this row block is not known yet; the guess is the block's first tile's sum times the
+                // tiles before the block (sr_fold_dev.h, SR_FCAND_N).  The first row block is always slow
+                // in the plan: nothing to do.
+                if (rb > 0 && a.fold_cand != nullptr) {
+                  using I = typename SrFoldTab<T>::I;
+                  constexpr I CAP = I(1) << (SrFoldTraits<T>::mant + 3);
+                  int32_t qh;
+                  if (tile == 0) {
+                    qh = sr_fold_q<T>(double(s) * double(a.tiles_per_block) * double(rb) * 0.7071067811865476);
+                    qh = __builtin_amdgcn_readfirstlane(qh);
+                    if (lane == j) cand_q = qh;
+                  } else {
+                    qh = __builtin_amdgcn_readlane(cand_q, j);
+                  }
+                  if (qh != SR_FCODE_SKIP) {
+                    I ct[SR_FCAND_N];
+                    bool cok[SR_FCAND_N];
+                    sr_fold_tile_fast_n<T, R, SR_FCAND_N>(lc, qh, ct, cok);
+#pragma unroll
+                    for (int c = 0; c < SR_FCAND_N; ++c) {
+                      const I x = __builtin_amdgcn_readlane(cand[c], j);
+                      const I n = (!cok[c] || x < 0) ? SR_FCAND_TIE : (x + ct[c] < CAP ? x + ct[c] : CAP);
+                      if (lane == j) cand[c] = n;
+                    }
+                  }
+                }
+              }
             }
           }
           if (dead) {
@@ -1504,6 +1558,11 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
     T* out = static_cast<T*>(a.range_sums);
     for (int i = tid; i < gcount * MC; i += SR_BLOCK) out[(size_t(tree0) * MC + i) * size_t(a.n_row_blocks) + rb] = jst[i];
     return;
+  }
+  if constexpr (CAND) {
+    if (a.fold_cand != nullptr && lane < S)
+      a.fold_cand[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)] =
+          make_int4(((dmask >> lane) & 1u) ? SR_FCODE_SKIP : cand_q, cand[0], cand[1], cand[2]);
   }
   if (lane < S) {
     uint32_t f = (((dmask >> lane) & 1u) ? SR_FLAG_NONFINITE : 0u) | (((bmask >> lane) & 1u) ? SR_FLAG_BIG : 0u) |

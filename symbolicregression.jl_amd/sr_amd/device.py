@@ -67,7 +67,8 @@ class DeviceContext:
         "code_cache", "timing", "rows_per_lane", "balance", "fused_reduce", "exact_w", "exact_g", "fold_seg",
         "ref_fold" (the in-order loss fold: 1 default, 0 the f64 sums), "fold_seg_max" / "fold_rows_max"
         (the longest row block / fold folded: past them a call keeps the f64 sums — these three are the
-        knobs results depend on), "fold_store_mb", "fold_slot_mb", "fold_delta_log2"; tests:
+        knobs results depend on), "fold_store_mb", "fold_slot_mb", "fold_delta_log2", "fold_single_pass" (the
+        loss launch of a FOLD-mode call composes the fold's steps under candidate binades: 1 default); tests:
         "inject_failure*", "debug_hint_regrow", "fold_debug_fail"."""
         _lib.check(_lib.lib.sr_set_tuning(self.handle, name.encode(), int(value)))
 
@@ -91,6 +92,13 @@ class DeviceContext:
         _lib.check(_lib.lib.sr_ref_fold_info(self.handle, ctypes.byref(p), ctypes.byref(a), ctypes.byref(b),
                                              ctypes.byref(ms)))
         return {"path": int(p.value), "folded": int(a.value), "fallback": int(b.value), "kernel_ms": float(ms.value)}
+
+    def last_fold_cand(self):
+        """The last FOLD-mode (path 2) call's (tree, row block) pairs: {taken: composed step taken from the
+        loss launch's candidate binades, rerun: run by the FOLD pass}; both 0 after any other call."""
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.lib.sr_last_fold_cand(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        return {"taken": int(a.value), "rerun": int(b.value)}
 
     def last_exact_kernel_ms(self):
         """Device time of the last eval_loss call's exact-sum pass (ms)."""
