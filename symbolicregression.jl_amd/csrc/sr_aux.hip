@@ -1359,38 +1359,6 @@ hipError_t sr_launch_pad(T* v, int64_t n, int64_t ld, T pad_value, int replicate
   return hipGetLastError();
 }
 
-// Rows per lane of each instantiated kernel (sr_inst_*.hip): f32 BASIC 8 (4 for tuning), f32 FULL 4,
-// f64 BASIC 4, f64 FULL 2.  `rows_per_lane` <= 0 picks the default.
-template <typename T>
-int sr_rows_per_lane(int mode, int tier, int requested) {
-  const bool basic = mode == SR_MODE_LOSS && tier == SR_TIER_BASIC;
-  if (sizeof(T) == 4) {
-    if (basic) return (requested == 4 || requested == 16) ? requested : 8;
-    return 4;
-  }
-  return basic ? 4 : 2;
-}
-template int sr_rows_per_lane<float>(int, int, int);
-template int sr_rows_per_lane<double>(int, int, int);
-
-size_t sr_tile_lds_bytes(int elem_size, int nf, int rows_per_lane, int stack_depth, int trees_per_block,
-                         int max_checks, int waves, bool weighted, int code_lds) {
-  // = SrLdsPlan (sr_tile_impl.h): X tile, y (+ w), LDS stack, EXACT checked values + running sums,
-  // program cache (16-byte instructions)
-  const size_t rows = size_t(64) * rows_per_lane;
-  return size_t(nf) * rows * elem_size + (weighted ? 2 : 1) * rows * elem_size +
-         size_t(waves) * stack_depth * rows * elem_size + size_t(waves) * size_t(max_checks) * rows * elem_size +
-         (size_t(trees_per_block) * size_t(max_checks) * elem_size + 15) / 16 * 16 + size_t(code_lds) * 16;
-}
-
-// Waves per workgroup: the f32 BASIC loss kernel has 4- and 8-wave (L2) builds (SR_AMD_WAVES selects);
-// every other kernel runs 4 waves.
-int sr_waves_per_block(int elem_size, int mode, int tier, int rows_per_lane, int requested) {
-  if (elem_size == 4 && mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && rows_per_lane == 8 && requested == 8)
-    return 8;
-  return 4;
-}
-
 // BASIC-tier loss kernels are built per elementwise loss (the loss code folds away).
 template <typename T, int R, bool GATHER, bool VSTK = false>
 hipError_t sr_launch_basic_loss(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s) {
@@ -1399,31 +1367,6 @@ hipError_t sr_launch_basic_loss(const SrEvalArgs<T>& a, int n_blocks, hipStream_
   if (a.loss_kind == SR_LOSS_L2)
     return sr_launch_tile<T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, SR_LOSS_L2, VSTK>(a, n_blocks, s);
   return sr_launch_tile<T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, -1, VSTK>(a, n_blocks, s);  // other losses
-}
-
-// Register-stack kernels (f32 BASIC loss over the full dataset, operand stack in VGPRs): rows per
-// lane for a view of n rows, or 0 when the classic LDS-stack kernel should run.  Larger tiles halve
-// the per-tree epilogues and dispatches per row and, with no LDS stack, keep the workgroup's LDS at
-// the X tile (C2 kernel -5 %, its complete trees -12 %, arithmetic-only -18 %); below
-// 2^17 rows the padding and the loss of parallelism cost more.  requested: SR_AMD_ROWS_PER_LANE
-// (16 / 32 force a register-stack kernel, 4 / 8 the classic one; f64: 8 selects its register-stack
-// build).
-#ifndef SR_VSTK_DEFAULT_ROWS
-#define SR_VSTK_DEFAULT_ROWS 16
-#endif
-int sr_vstk_rows(int elem_size, int64_t n_rows, int requested) {
-  // f64: the 8-rows/lane register-stack build (181 VGPRs, 2 waves per SIMD) against the classic
-  // 4-rows/lane build (100, 5 waves): round 2 measured it 3 % slower; with the launch order dealt over
-  // tree groups it is faster (C2 in f64 13.45 -> 12.69 ms per step, arithmetic-only -19 %,
-  // profiles/r03_ab_f64_vstk.txt), so it is the default for large views too
-  if (elem_size == 8) {
-    if (requested == 8 || requested == -4) return requested == 8 ? 8 : 4;  // (-4: the 4-row register-stack build)
-    if (requested == 4 || requested == 2) return 0;
-    return n_rows >= (int64_t(1) << 17) ? 8 : 0;
-  }
-  if (requested == 16 || requested == 32) return requested;
-  if (requested == 4 || requested == 8) return 0;
-  return n_rows >= (int64_t(1) << 17) ? SR_VSTK_DEFAULT_ROWS : 0;
 }
 
 template <typename T>

@@ -106,7 +106,6 @@ struct HostBuf {
   }
 };
 
-constexpr int kMaxChunks = 4;
 constexpr int kLossCodeBase = 256;
 
 // Parameter-free losses (and HuberLoss with its default delta = 1) may be passed by kind.
@@ -397,42 +396,6 @@ constexpr int kProbeTiles = 4;  // row tiles of a dead-tree probe launch
 // libm tables, 4 workgroups still fit a CU's 160 KiB
 constexpr size_t kCodeCacheLds = 34 * 1024;
 
-// Work decomposition: row tiles of 64*R rows (one LDS image each), `tiles` per block; trees grouped G
-// per block (the block's 4 waves share the G trees of a tile).
-struct Grid {
-  int G = 32, tiles = 1, n_row_blocks = 1, n_groups = 1, R = 8, W = 4;
-  int64_t n_blocks = 1;
-  size_t lds = 0;
-};
-constexpr size_t kLdsMax = 160 * 1024;
-template <typename T>
-Grid make_grid(int64_t n_rows, int64_t n_trees, int R, int W, int nf, int depth, int max_checks, bool weighted,
-               int g_override = 0, int max_row_blocks = 256) {
-  const int64_t rows_per_tile = 64 * int64_t(R);
-  Grid g;
-  g.R = R;
-  g.W = W;
-  const int64_t n_tiles = (n_rows + rows_per_tile - 1) / rows_per_tile;
-  int64_t tiles = (n_tiles + max_row_blocks - 1) / max_row_blocks;  // keep <= max row blocks per tree
-  if (tiles < 1) tiles = 1;
-  g.tiles = int(tiles);
-  g.n_row_blocks = int((n_tiles + tiles - 1) / tiles);
-  if (g.n_row_blocks < 1) g.n_row_blocks = 1;
-  // more trees per tile amortise the tile's LDS staging and barriers (G 16 -> 128: -29% kernel time
-  // on the C2 population); shrink only to keep >= 4096 workgroups for small populations
-  int G = 128;
-  while (G > 4 && int64_t(g.n_row_blocks) * ((n_trees + G - 1) / G) < 4096) G /= 2;
-  if (g_override > 0) G = g_override;
-  if (G < W) G = W;  // at least one tree per wave
-  if (n_trees > 0 && G > n_trees) G = int(n_trees);
-  if (G < 1) G = 1;
-  g.G = G;
-  g.n_groups = int((n_trees + G - 1) / G);
-  g.n_blocks = int64_t(g.n_row_blocks) * g.n_groups;
-  g.lds = sr_tile_lds_bytes(int(sizeof(T)), nf, R, depth, G, max_checks, W, weighted);
-  return g;
-}
-
 template <typename T>
 double t_max() {
   return double(SrM<T>::big);
@@ -477,55 +440,6 @@ int decode_loss(sr_ctx* ctx, int code, int* kind, double* param) {
   return SR_OK;
 }
 
-// Shared engine: compile + upload + interpreter(+reduce).  Leaves per-tree {sum, flag} in
-// ctx->d_out_sum / ctx->d_out_flag (device).  n_eval rows (full dataset or row_idx view).
-//
-// Large LOSS batches are pipelined in up to kMaxChunks tree chunks: the host compiles chunk c+1
-// while the device runs chunk c (programs staged through pinned memory, async DMA).  Every chunk is
-// an independent launch over its own slice of the per-tree device arrays; `prog` receives the merged
-// per-tree summary (offsets into the device code buffer, static_bad, max_depth, max_checks) that
-// the exact-sum pass and the callers use — its `code` stays empty.
-// Derived columns of a LOSS call: the unary(feature) nodes of the batch's transcendental operators
-// (exp / cos / sin / safe_log / safe_sqrt) that at least kDerivedMinUses trees of a sample share,
-// most used first, at most SR_MAX_DERIVED.  dmap: [SR_U_COUNT][nf] -> column or -1.
-constexpr int64_t kDerivedMinRows = 16384;  // below this the per-call column pass does not pay
-constexpr int kDerivedMinUses = 4;
-constexpr double kDerivedMinWork = 33554432.0;  // trees x rows (2^25) below which the column pass does not pay
-constexpr int64_t kDerivedSample = 1024;    // trees scanned
-void choose_derived(const sr_tree_batch& trees, const SrOpset& ops, int64_t nf, SrDerivedSpec* spec,
-                    std::vector<int16_t>* dmap) {
-  spec->n = 0;
-  dmap->assign(size_t(SR_U_COUNT) * size_t(nf), int16_t(-1));
-  auto eligible = [](uint32_t u) {
-    return u == SR_U_EXP || u == SR_U_COS || u == SR_U_SIN || u == SR_U_LOG || u == SR_U_SQRT;
-  };
-  std::vector<int32_t> uses(size_t(SR_U_COUNT) * size_t(nf), 0);
-  const int64_t ns = trees.n_trees < kDerivedSample ? trees.n_trees : kDerivedSample;
-  for (int64_t k = 0; k < ns; ++k) {
-    const int64_t b = trees.offsets[k], e = trees.offsets[k + 1];
-    // pre-order: node i (degree 1) has its child at i + 1
-    for (int64_t i = b; i + 1 < e; ++i) {
-      if (trees.degree[i] != 1 || trees.degree[i + 1] != 0 || trees.constant[i + 1]) continue;
-      const int oi = int(trees.op[i]) - 1;
-      const int f = int(trees.feature[i + 1]) - 1;
-      if (oi < 0 || oi >= int(ops.unary.size()) || f < 0 || f >= nf) continue;
-      const uint32_t u = ops.unary[size_t(oi)];
-      if (eligible(u)) ++uses[size_t(u) * size_t(nf) + size_t(f)];
-    }
-  }
-  std::vector<std::pair<int32_t, size_t>> cand;
-  for (size_t q = 0; q < uses.size(); ++q)
-    if (uses[q] >= kDerivedMinUses) cand.push_back({uses[q], q});
-  std::stable_sort(cand.begin(), cand.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
-  for (const auto& c : cand) {
-    if (spec->n >= SR_MAX_DERIVED) break;
-    const int k = spec->n++;
-    spec->op[k] = uint8_t(c.second / size_t(nf));
-    spec->feat[k] = uint16_t(c.second % size_t(nf));
-    (*dmap)[c.second] = int16_t(k);
-  }
-}
-
 // Row-sharded calls decide data-dependent launch choices from the statistics of ALL shards, so every
 // rank compiles identical programs (same derived columns: the exact path numbers checked arrays the
 // same on every rank): max|X| over every shard and the smallest shard's row count.
@@ -558,9 +472,13 @@ struct FoldRegion {
   int Rc;
   bool vstk;
   Grid g;
+  int64_t rb_rows() const { return int64_t(g.tiles) * 64 * Rc; }
+  // the region's offset in the partial buffers of n_rb row blocks per position, and its plan arrays there
+  size_t off(int64_t n_rb) const { return size_t(n_rb) * size_t(pos0); }
+  SrFoldTabs tabs(sr_ctx* ctx, int64_t n_rb) const;
 };
 // A call's fold: its regions and the launch facts every fold kernel needs (kept by a row-sharded call's
-// run_batch until the ranks have agreed on the verdicts: FoldJob::deferred).
+// batch engine until the ranks have agreed on the verdicts: FoldJob::deferred).
 template <typename T>
 struct FoldJob {
   std::vector<FoldRegion<T>> regions;
@@ -580,6 +498,21 @@ SrFoldTabs fold_tabs(sr_ctx* ctx, size_t off) {
   return SrFoldTabs{ctx->fold_code.as<int32_t>() + off, ctx->fold_tab.as<char>() + off * sizeof(Pair),
                     ctx->fold_sq.as<int32_t>() + off, ctx->fold_tab2.as<char>() + off * sizeof(Pair)};
 }
+template <typename T>
+SrFoldTabs FoldRegion<T>::tabs(sr_ctx* ctx, int64_t n_rb) const {
+  return fold_tabs<T>(ctx, off(n_rb));
+}
+// the call's whole-batch arrays (sums / flags / elig / est / the pinned mirrors at the caller's tree
+// index) from a region's chunk offset on
+inline SrFoldWho fold_who_at(SrFoldWho who, int64_t t0) {
+  if (who.sums) who.sums += t0;
+  if (who.flags) who.flags += t0;
+  if (who.elig) who.elig += t0;
+  if (who.est) who.est += t0;
+  if (who.msum) who.msum += t0;
+  if (who.mflag) who.mflag += t0;
+  return who;
+}
 // A stored-loss call of one row block of at most 256 rows that starts the fold (C1's 100-row calls): the
 // walk's serial start folds every row and takes eligibility from the call's flags itself, so the pair
 // kernel's launch is skipped (round 6: ~5 us of a ~45 us call)
@@ -589,26 +522,20 @@ bool fold_tiny(const FoldJob<T>& job, const FoldRegion<T>& fr, const SrFoldWho& 
          who.est == nullptr;
 }
 // A region's steps: the stored-loss tables (path 1) or the plan and the FOLD pass (path 2).  who: the
-// call's whole-batch arrays (sums / flags / elig / est at the caller's tree index; this function adds
-// the region's chunk offset).
+// call's whole-batch arrays (this function adds the region's chunk offset).
 template <typename T>
 int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFoldWho who, hipStream_t cs) {
   const int nrb = fr.g.n_row_blocks;
-  const int64_t rb_rows = int64_t(fr.g.tiles) * 64 * fr.Rc;
-  const size_t off = size_t(job.n_rb) * size_t(fr.pos0);  // (the region's offset in the partial buffers)
-  const SrFoldTabs ft = fold_tabs<T>(ctx, off);
+  const SrFoldTabs ft = fr.tabs(ctx, job.n_rb);
   const double* part = nrb > 1 ? fr.a.part_sum : nullptr;
   const int np = int(fr.np);
-  if (who.sums) who.sums += fr.t0;
-  if (who.flags) who.flags += fr.t0;
-  if (who.elig) who.elig += fr.t0;
-  if (who.est) who.est += fr.t0;
+  who = fold_who_at(who, fr.t0);
   if (job.path == 1) {
     if (fold_tiny(job, fr, who)) return SR_OK;  // (the walk's serial start is the whole fold: no pairs)
     const bool fr_red = job.fuse_reduce && nrb > 1;
-    SR_HIP_CHECK(sr_launch_fold_stab<T>(part, np, nrb, rb_rows, job.n_eval, fr.a.perm, who, job.delta, fr.a.fold_loss,
-                                        ft, fr_red ? fr.a.part_flag : nullptr, fr_red ? ctx->d_bad + fr.t0 : nullptr,
-                                        fr_red ? ctx->d_out_sum + fr.t0 : nullptr,
+    SR_HIP_CHECK(sr_launch_fold_stab<T>(part, np, nrb, fr.rb_rows(), job.n_eval, fr.a.perm, who, job.delta,
+                                        fr.a.fold_loss, ft, fr_red ? fr.a.part_flag : nullptr,
+                                        fr_red ? ctx->d_bad + fr.t0 : nullptr, fr_red ? ctx->d_out_sum + fr.t0 : nullptr,
                                         fr_red ? ctx->d_out_flag + fr.t0 : nullptr, cs));
     return SR_OK;
   }
@@ -643,75 +570,161 @@ int fold_walk(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFol
   const int tiny = carry == nullptr && fold_tiny(job, fr, who) ? 16 : 0;
   // (stored losses, the pair kernel launched, the fold starting here: it did the serial start)
   const int pre = job.path == 1 && !tiny && carry == nullptr && who.first && ctx->fold_pre_start ? 32 : 0;
-  if (who.sums) who.sums += fr.t0;
-  if (who.flags) who.flags += fr.t0;
-  if (who.elig) who.elig += fr.t0;
-  if (who.est) who.est += fr.t0;
-  if (who.msum) who.msum += fr.t0;
-  if (who.mflag) who.mflag += fr.t0;
-  const int64_t rb_rows = int64_t(fr.g.tiles) * 64 * fr.Rc;
-  const size_t off = size_t(job.n_rb) * size_t(fr.pos0);
-  const SrFoldTabs ft = fold_tabs<T>(ctx, off);
+  who = fold_who_at(who, fr.t0);
+  const int64_t rb_rows = fr.rb_rows();
+  const SrFoldTabs ft = fr.tabs(ctx, job.n_rb);
   const T* losses = job.path == 1 ? fr.a.fold_loss : ctx->fold_store.as<T>();
   const int64_t slot_rows = job.path == 1 ? rb_rows : job.slot_rows;
   int4* dbg = ctx->fold_stats ? ctx->fold_dbg.as<int4>() + fr.t0 : nullptr;  // (SR_AMD_FOLD_STATS)
-  SR_HIP_CHECK(sr_launch_fold_walk<T>(ft, who, int(fr.np), nrb, rb_rows, job.n_eval, losses, slot_rows, fr.a.perm,
-                                      carry ? carry + fr.t0 : nullptr, out_val + fr.t0, out_st + fr.t0, dbg,
-                                      int(job.path == 1) | tiny | pre | ctx->fold_walk_dbg, cs));
-  if (ctx->fold_stats == 2)  // (analysis: the same walk again, its loads now warm: the statistics are the second's)
+  // (fold_stats 2, analysis: the same walk again, its loads now warm: the statistics are the second's)
+  for (int pass = 0; pass < (ctx->fold_stats == 2 ? 2 : 1); ++pass)
     SR_HIP_CHECK(sr_launch_fold_walk<T>(ft, who, int(fr.np), nrb, rb_rows, job.n_eval, losses, slot_rows, fr.a.perm,
                                         carry ? carry + fr.t0 : nullptr, out_val + fr.t0, out_st + fr.t0, dbg,
                                         int(job.path == 1) | tiny | pre | ctx->fold_walk_dbg, cs));
   return SR_OK;
 }
 
+// ---------------------------------------------------------------- the batch engine
+// Shared engine: compile + upload + interpreter(+reduce).  Leaves per-tree {sum, flag} in
+// ctx->d_out_sum / ctx->d_out_flag (device).  n_eval rows (full dataset or row_idx view).
+//
+// Large LOSS batches are pipelined in up to kMaxChunks tree chunks: the host compiles chunk c+1
+// while the device runs chunk c (programs staged through pinned memory, async DMA).  Every chunk is
+// an independent launch over its own slice of the per-tree device arrays; `prog` receives the merged
+// per-tree summary (offsets into the device code buffer, static_bad, max_depth, max_checks) that
+// the exact-sum pass and the callers use — its `code` stays empty.
+//
+// run_batch is a driver over the stages below (DESIGN.md §4.6 lists them in order); the host-only
+// decisions — grids, chunks, launch order, code layout, segments, the fold's path — are sr_plan.h's.
+// One tree chunk [t0, t0 + nc) of a call: its compiled programs and launch plan.
 template <typename T>
-int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, const int64_t* row_idx,
-              int64_t n_idx, int64_t n_total, int loss_kind, int mode, SrProgramBatch<T>* prog, Grid* grid_out,
-              bool allow_derived = false, const ShardCtl* shard = nullptr, const ViewSpec* views = nullptr) {
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  // PRED passes (the fold's few band trees) write no partials: more row blocks fill the GPU (C4's 14 trees
-  // x 2^26 rows ran 1,024 workgroups at 256)
-  int mrb = mode == SR_MODE_PRED ? std::max(ctx->max_row_blocks, 4096) : ctx->max_row_blocks;
-  const int64_t n_eval = gather ? n_idx : ds->n;
-  if (n_eval <= 0) return set_error(SR_ERR_INVALID_ARG, "no rows to evaluate");
-  // under the in-order fold, row blocks of at most fold_seg_max rows on the largest shard (every rank
-  // the same count): a slow block's rows are kept whole (C4's 2^26 rows per GPU: 4,096 blocks of 16k)
-  if (mode == SR_MODE_LOSS && ctx->want_fold && ctx->ref_fold && sizeof(T) == 4 && ctx->fold_seg_max > 0 &&
-      (shard ? n_total : n_eval) <= ctx->fold_rows_max) {
-    int64_t max_rows = n_eval;
-    if (shard)
-      for (size_t r = 0; r + 1 < ds->shard_offs.size(); ++r) max_rows = std::max(max_rows, ds->shard_offs[r + 1] - ds->shard_offs[r]);
-    const int64_t need = (max_rows + ctx->fold_seg_max - 1) / ctx->fold_seg_max;
-    if (need > mrb) mrb = int(std::min<int64_t>(need, 16384));
-  }
-  // several views: one launch, its tree groups view-pure (SrSegment); rows uploaded for every view
-  const bool multi = views != nullptr && gather && mode == SR_MODE_LOSS;
-  const int64_t n_rows_up = multi ? int64_t(views->n_views) * n_idx : n_idx;
-  if (multi) allow_derived = false;
-  int lkind = 0;
+struct BatchChunk {
+  int c = 0;
+  int64_t t0 = 0, nc = 0;
+  uint32_t max_nodes = 1;  // the chunk's largest tree (bounds the untracked values: SR_TRACK_LITE)
+  hipStream_t cs = nullptr;
+  SrProgramBatch<T> pc;
+  int depth = 1;
+  size_t ncode = 0;
+  int64_t n_vs = 0;  // launch positions [0, n_vs) -> register-stack kernel
+  Grid g_vs, g_ls;   // the grids of its two launches: [0, n_vs) at Rv, [n_vs, nc) at R — the deal's, the
+                     // segments' and the launch's alike
+  int n_seg = 0;
+  int64_t seg_blocks = 0;
+};
+
+#define SR_STAGE(expr)           \
+  do {                           \
+    const int _rc = (expr);      \
+    if (_rc != SR_OK) return _rc; \
+  } while (0)
+
+// One call's state, written by the stages in order, and the stages (run() calls them).
+template <typename T>
+struct BatchCall {
+  // the inputs
+  sr_ctx* ctx;
+  const sr_dataset* ds;
+  int opset_id;
+  const sr_tree_batch* trees;
+  const int64_t* row_idx;
+  int64_t n_idx, n_total;
+  int loss_kind, mode;
+  SrProgramBatch<T>* prog;
+  bool allow_derived;
+  const ShardCtl* shard;
+  const ViewSpec* views;
+  // validate_call: the view, the decoded loss, the batch's size
+  bool gather = false, multi = false;
+  int64_t n_eval = 0, n_rows_up = 0, nt = 0, total_nodes = 0;
+  int mrb = 0, lkind = 0;  // (mrb: the row-block bound of the call's grids)
   double lparam = 0.0;
-  if (decode_loss(ctx, loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
-  const int64_t nt = trees->n_trees;
-  if (nt < 0) return set_error(SR_ERR_INVALID_ARG, "negative tree count");
-  if (nt > 0 && !trees->offsets) return set_error(SR_ERR_INVALID_ARG, "sr_tree_batch has NULL arrays");
-  const int64_t total_nodes = nt > 0 ? trees->offsets[nt] - trees->offsets[0] : 0;
-  if (total_nodes < 0 || total_nodes > int64_t(0xffffffffu) / 2)
-    return set_error(SR_ERR_INVALID_ARG, "tree batch node count out of range");
-  // (SR_TRACK_LITE: the deferred-check kernels bound untracked values by L x max|x| for trees of up to
-  //  L nodes; data at or above tbig / L — huge or non-finite values, never seen in practice — runs the
-  //  per-node-check kernels instead, whose checks hold for any data)
-  // A parametric call (sr_ctx::param): the table the kernels gather from, [tree][parameter][class] in T
-  // (each tree's Julia column-major matrix transposed, so that one parameter's classes are contiguous),
-  // staged in pinned memory here and uploaded below; the leaf bound of the deferred checks becomes
-  // max(max|X|, max|P|), Inf when any entry is non-finite (then, as for such data, the per-node-check
-  // tier runs: DESIGN.md §4.6).  nfk: the X rows a launch stages (the hidden class row included).
-  const sr_param_batch* const pb = ctx->param;
-  const bool parametric = pb != nullptr;
-  const int nfk = int(ds->nf) + (parametric ? 1 : 0);
+  // stage_param_table: a parametric call's table facts (nfk: the X rows a launch stages)
+  const sr_param_batch* pb = nullptr;
+  bool parametric = false;
+  int nfk = 0;
   int64_t p_stride = 0;
   double max_abs_p = 0.0;
-  if (parametric) {
+  // choose_kernels: tier, rows per lane (classic R, register-stack Rv or 0), waves; every grid's spec;
+  // row blocks the partial buffers hold per tree (the most any kernel uses); the chunks
+  int tier = 0, R = 0, W = 0, Rv = 0, n_rb = 1, n_chunks = 1;
+  GridSpec gs;
+  Grid g_ls, g_vs;  // the whole batch's grids at R (depth 1) and, Rv > 0, at Rv (depth 0)
+  Grid glast;       // the last launch's (the callers' grid_out)
+  // bind_buffers: the staging image's layout, its device and pinned copies, the partials' count
+  ProgImage img;
+  size_t n_part = 0;
+  char *dprog = nullptr, *hprog = nullptr;
+  SrIns<T>* h_code = nullptr;
+  uint32_t *h_off = nullptr, *h_perm = nullptr, *h_end = nullptr;
+  uint8_t* h_bad = nullptr;
+  // plan_fold / bind_outputs / prepare_hints
+  int64_t fold_n_terms = 0;
+  FoldPlan fold;
+  bool fold_cand = false;
+  bool host_out = false, fold_mirror = false, host_red = false, use_hint = false, use_probe = false, stress_probe = false;
+  // launch_derived: the derived-column spec and map, the columns' leading dimension, the call's leaf bound
+  std::vector<int16_t> dmap;
+  SrDerivedSpec spec{};
+  int64_t dld = 0;
+  double max_abs_x = 0.0;
+  // the chunks
+  FoldJob<T> fjob;  // (the regions of the chunk being launched; a row-sharded call's: all of them, kept)
+  size_t fold_store_at = 0;  // (stored losses: the regions one after another, [position][n_rb x rb rows])
+  T* d_fval = nullptr;
+  int32_t* d_fst = nullptr;
+  uint32_t code_base = 0;
+  std::chrono::steady_clock::time_point t_pre;
+  std::string err;
+  hipStream_t s = nullptr;
+  bool in_flight = false;  // the call has enqueued asynchronous work: an error exit joins both streams
+
+  // the largest leaf value of the call, as the deferred checks bound it
+  double leaf_bound(double max_abs_x_data) const { return parametric ? std::max(max_abs_x_data, max_abs_p) : max_abs_x_data; }
+  // Σ over n_total rows of values below tbig cannot overflow T, even with rounding slack.
+  T tbig() const { return T(t_max<T>() / (2.0 * double(n_total > 0 ? n_total : 1))); }
+
+  // The view, the row-block bound, the loss and the batch's size.
+  int validate_call() {
+    gather = row_idx != nullptr && n_idx > 0;
+    // PRED passes (the fold's few band trees) write no partials: more row blocks fill the GPU (C4's 14 trees
+    // x 2^26 rows ran 1,024 workgroups at 256)
+    mrb = mode == SR_MODE_PRED ? std::max(ctx->max_row_blocks, 4096) : ctx->max_row_blocks;
+    n_eval = gather ? n_idx : ds->n;
+    if (n_eval <= 0) return set_error(SR_ERR_INVALID_ARG, "no rows to evaluate");
+    // under the in-order fold, row blocks of at most fold_seg_max rows on the largest shard (every rank
+    // the same count): a slow block's rows are kept whole (C4's 2^26 rows per GPU: 4,096 blocks of 16k)
+    if (mode == SR_MODE_LOSS && ctx->want_fold && ctx->ref_fold && sizeof(T) == 4 && ctx->fold_seg_max > 0 &&
+        (shard ? n_total : n_eval) <= ctx->fold_rows_max) {
+      const int64_t max_rows = shard ? sr_max_shard_rows(ds->shard_offs, n_eval) : n_eval;
+      const int64_t need = (max_rows + ctx->fold_seg_max - 1) / ctx->fold_seg_max;
+      if (need > mrb) mrb = int(std::min<int64_t>(need, 16384));
+    }
+    // several views: one launch, its tree groups view-pure (SrSegment); rows uploaded for every view
+    multi = views != nullptr && gather && mode == SR_MODE_LOSS;
+    n_rows_up = multi ? int64_t(views->n_views) * n_idx : n_idx;
+    if (multi) allow_derived = false;
+    if (decode_loss(ctx, loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
+    nt = trees->n_trees;
+    if (nt < 0) return set_error(SR_ERR_INVALID_ARG, "negative tree count");
+    if (nt > 0 && !trees->offsets) return set_error(SR_ERR_INVALID_ARG, "sr_tree_batch has NULL arrays");
+    total_nodes = nt > 0 ? trees->offsets[nt] - trees->offsets[0] : 0;
+    if (total_nodes < 0 || total_nodes > int64_t(0xffffffffu) / 2)
+      return set_error(SR_ERR_INVALID_ARG, "tree batch node count out of range");
+    return SR_OK;
+  }
+
+  // A parametric call (sr_ctx::param): the table the kernels gather from, [tree][parameter][class] in T
+  // (each tree's Julia column-major matrix transposed, so that one parameter's classes are contiguous),
+  // staged in pinned memory here and uploaded by begin_programs; the leaf bound of the deferred checks
+  // becomes max(max|X|, max|P|), Inf when any entry is non-finite (then, as for such data, the
+  // per-node-check tier runs: DESIGN.md §4.6).  nfk: the X rows a launch stages (the hidden class row
+  // included).
+  int stage_param_table() {
+    pb = ctx->param;
+    parametric = pb != nullptr;
+    nfk = int(ds->nf) + (parametric ? 1 : 0);
+    if (!parametric) return SR_OK;
     if (shard) return set_error(SR_ERR_INVALID_ARG, "parametric trees are not supported by the sharded calls");
     if (ds->n_classes <= 0) return set_error(SR_ERR_INVALID_ARG, "a parametric call needs a dataset uploaded with classes");
     if (pb->n_classes != ds->n_classes)
@@ -729,6 +742,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
     T* hp = ctx->h_ptab.as<T>();
     const T* src = static_cast<const T*>(pb->parameters);
     bool bad = false;
+    double mp = 0.0;
     for (int64_t t = 0; t < nt; ++t)
       for (int64_t c = 0; c < NC; ++c)
         for (int64_t k = 0; k < K; ++k) {
@@ -736,375 +750,351 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
           hp[size_t(t) * size_t(p_stride) + size_t(k * NC + c)] = v;
           const double m = std::fabs(double(v));
           bad |= !std::isfinite(m);
-          max_abs_p = m > max_abs_p ? m : max_abs_p;
+          mp = m > mp ? m : mp;
         }
-    if (bad) max_abs_p = double(INFINITY);
+    max_abs_p = bad ? double(INFINITY) : mp;
     allow_derived = false;  // (derived columns are chosen for plain populations: not measured here)
+    return SR_OK;
   }
-  // the largest leaf value of the call, as the deferred checks bound it
-  auto leaf_bound = [&](double max_abs_x_data) { return parametric ? std::max(max_abs_x_data, max_abs_p) : max_abs_x_data; };
-  int tier = ctx->tiers[opset_id];
+
+  // The kernels of the call: the tier, rows per lane and waves; then every grid's spec, the row blocks of
+  // the partial buffers and the chunk count.
+  void choose_kernels() {
+    // (SR_TRACK_LITE: the deferred-check kernels bound untracked values by L x max|x| for trees of up to
+    //  L nodes; data at or above tbig / L — huge or non-finite values, never seen in practice — runs the
+    //  per-node-check kernels instead, whose checks hold for any data)
+    tier = ctx->tiers[opset_id];
 #ifdef SR_TRACK_LITE
-  if (tier == SR_TIER_BASIC && mode == SR_MODE_LOSS && nt > 0) {
-    int64_t lmax = 1;
-    for (int64_t t = 0; t < nt; ++t) lmax = std::max<int64_t>(lmax, trees->offsets[t + 1] - trees->offsets[t]);
-    const double mx = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
-    if (!(mx < double(T(t_max<T>() / (2.0 * double(n_total > 0 ? n_total : 1)))) / double(lmax))) tier = SR_TIER_FULL;
-  }
+    if (tier == SR_TIER_BASIC && mode == SR_MODE_LOSS && nt > 0) {
+      int64_t lmax = 1;
+      for (int64_t t = 0; t < nt; ++t) lmax = std::max<int64_t>(lmax, trees->offsets[t + 1] - trees->offsets[t]);
+      const double mx = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
+      if (!(mx < double(tbig()) / double(lmax))) tier = SR_TIER_FULL;
+    }
 #endif
-  // (a parametric call's kernels are a smaller set, sr_launch_eval_param: the classic kernel at its
-  //  default rows per lane, 4 waves, one register-stack build per type; its knobs map onto that set)
-  const int R = sr_rows_per_lane<T>(mode, tier, parametric ? 0 : ctx->rows_override);
-  const int W = parametric ? 4 : sr_waves_per_block(int(sizeof(T)), mode, tier, R, ctx->waves_override);
-  // register-stack kernel (f32 BASIC loss over the full dataset): Rv rows per lane, used for every
-  // chunk whose programs need <= 2 operand-stack slots (all trees of <= 30 nodes); other chunks run
-  // the LDS-stack kernel at R rows per lane
-  int Rv = (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && !gather)
+    // (a parametric call's kernels are a smaller set, sr_launch_eval_param: the classic kernel at its
+    //  default rows per lane, 4 waves, one register-stack build per type; its knobs map onto that set)
+    R = sr_rows_per_lane<T>(mode, tier, parametric ? 0 : ctx->rows_override);
+    W = parametric ? 4 : sr_waves_per_block(int(sizeof(T)), mode, tier, R, ctx->waves_override);
+    // register-stack kernel (f32 BASIC loss over the full dataset): Rv rows per lane, used for every
+    // chunk whose programs need <= 2 operand-stack slots (all trees of <= 30 nodes); other chunks run
+    // the LDS-stack kernel at R rows per lane
+    Rv = (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && !gather)
                ? sr_vstk_rows(int(sizeof(T)), n_eval, ctx->vstk_rows ? ctx->vstk_rows : ctx->rows_override)
                : 0;
-  if (parametric && Rv > 0) Rv = sizeof(T) == 4 ? 16 : 8;  // (the one register-stack build of a parametric call)
-  // a wide dataset whose register-stack tile (its rows per lane are twice the classic kernel's) would
-  // not fit the LDS runs the classic kernel instead (Float64 with ~40-75 features)
-  if (Rv > 0 && make_grid<T>(n_eval, nt > 0 ? nt : 1, Rv, W, nfk, 0, 0, ds->w != nullptr, ctx->tree_group,
-                             mrb).lds > kLdsMax)
-    Rv = 0;
-  ctx->rows_last = Rv > 0 ? Rv : R;  // (every C2-like tree fits the register stack)
-  hipStream_t s = ctx->stream;
-  // error exits while chunks are in flight: no DMA may still read the staging buffers
-  auto sync_both = [&] {
-    (void)hipStreamSynchronize(s);
-    if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-  };
-
-  // chunking (SR_AMD_CHUNKS, default 2; LOSS mode only — PRED writes rows by caller tree index).
-  // Default: a first chunk of 1/6 of the trees runs while the host compiles the rest (exposed compile
-  // 0.72 -> 0.27 ms on C2, every test population's step faster).  k > 2 equal chunks (>= 2048 trees
-  // each) alternate over the two streams; they cost kernel time on complete-heavy populations.
-  constexpr int64_t kChunkTrees = 2048;
-  int n_chunks = 1;
-  if (multi) {
-    // (one chunk: the segments cover the whole launch)
-  } else if (mode == SR_MODE_LOSS && ctx->chunks == 2) {
-    n_chunks = nt / ctx->first_chunk >= ctx->chunk_min ? 2 : 1;  // the small first chunk holds >= chunk_min trees
-  } else if (mode == SR_MODE_LOSS && ctx->chunks > 2) {
-    const int64_t k = nt / kChunkTrees;
-    const int64_t cap = ctx->chunks < kMaxChunks ? ctx->chunks : kMaxChunks;
-    n_chunks = int(k < 1 ? 1 : (k > cap ? cap : k));
+    if (parametric && Rv > 0) Rv = sizeof(T) == 4 ? 16 : 8;  // (the one register-stack build of a parametric call)
+    // every grid of the call comes from this one spec
+    gs = GridSpec{int(sizeof(T)), n_eval, W, nfk, ds->w != nullptr, ctx->tree_group, mrb};
+    // a wide dataset whose register-stack tile (its rows per lane are twice the classic kernel's) would
+    // not fit the LDS runs the classic kernel instead (Float64 with ~40-75 features)
+    if (Rv > 0) {
+      g_vs = gs.grid(nt > 0 ? nt : 1, Rv, 0);
+      if (g_vs.lds > kLdsMax) Rv = 0;
+    }
+    ctx->rows_last = Rv > 0 ? Rv : R;  // (every C2-like tree fits the register stack)
+    n_chunks = sr_chunk_count(nt, ctx->chunks, ctx->first_chunk, ctx->chunk_min, multi, mode);
+    g_ls = gs.grid(nt > 0 ? nt : 1, R, 1);
+    glast = g_ls;
+    n_rb = g_ls.n_row_blocks;
+    if (Rv > 0) n_rb = std::max(n_rb, g_vs.n_row_blocks);
   }
 
   // device + pinned buffers sized for the whole batch up front (a chunk's kernel may still run while
   // the next one is staged): a program has at most one instruction per node
-  Grid g0 = make_grid<T>(n_eval, nt > 0 ? nt : 1, R, W, nfk, 1, 0, ds->w != nullptr, ctx->tree_group,
-                         mrb);
-  int n_rb = g0.n_row_blocks;  // row blocks the partial buffers hold per tree (the most any kernel uses)
-  if (Rv > 0)
-    n_rb = std::max(n_rb, make_grid<T>(n_eval, nt > 0 ? nt : 1, Rv, W, nfk, 0, 0, ds->w != nullptr,
-                                       ctx->tree_group, mrb).n_row_blocks);
-  const size_t code_cap = size_t(total_nodes) + 16;
-  auto align256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t o_off = align256(code_cap * sizeof(SrIns<T>));
-  const size_t o_bad = align256(o_off + (size_t(nt) + 1) * sizeof(uint32_t));
-  const size_t o_perm = align256(o_bad + size_t(nt) + 16);
-  const size_t o_end = align256(o_perm + (size_t(nt) + 1) * sizeof(uint32_t));
-  const size_t o_seg = align256(o_end + (size_t(nt) + 1) * sizeof(uint32_t));
-  const size_t n_seg_cap = multi ? size_t(views->n_views) : 0;
-  const size_t prog_bytes = o_seg + n_seg_cap * sizeof(SrSegment);
-  SR_HIP_CHECK(ctx->prog.ensure(prog_bytes));
-  SR_HIP_CHECK(ctx->h_prog.ensure(prog_bytes, s, ctx->stream2));
-  char* const dprog = ctx->prog.as<char>();
-  ctx->d_code = dprog;
-  ctx->d_off = reinterpret_cast<uint32_t*>(dprog + o_off);
-  ctx->d_bad = reinterpret_cast<uint8_t*>(dprog + o_bad);
-  ctx->d_perm = reinterpret_cast<uint32_t*>(dprog + o_perm);
-  ctx->d_end = reinterpret_cast<uint32_t*>(dprog + o_end);
-  const size_t n_part = size_t(nt) * size_t(n_rb);
-  SR_HIP_CHECK(ctx->part_sum.ensure(n_part * sizeof(double) + 8));
-  SR_HIP_CHECK(ctx->part_flag.ensure(n_part * sizeof(uint32_t) + 4));
-  if (mode == SR_MODE_LOSS && ctx->fused_reduce > 0 && size_t(nt) * sizeof(uint32_t) + 4 > ctx->group_cnt.cap) {
-    SR_HIP_CHECK(hipStreamSynchronize(s));  // (the second stream runs only inside a call)
-    SR_HIP_CHECK(ctx->group_cnt.ensure(size_t(nt) * sizeof(uint32_t) + 4));
-    SR_HIP_CHECK(hipMemset(ctx->group_cnt.p, 0, ctx->group_cnt.cap));
-  }
-  // the reference's in-order loss fold of every complete tree (sr_ctx::ref_fold): 1 = the loss launch
-  // stores every tree's losses (they fit fold_store_mb), 2 = the FOLD-mode pass over the complete trees
-  // (a row-sharded call: the global rows and every shard's weights; its ranks fold or not together —
-  //  the choice below depends on the largest shard's rows, known to every rank)
-  const int64_t fold_n_terms = shard ? ((ds->w && ds->shard_w_min < 0.0) ? 0 : n_total) : fold_terms(ds, n_eval);
-  int fold_path = 0;
-  int64_t fold_slot_rows = 0, fold_slots = 0;
-  if (shard) ctx->fold_job.reset();
-  if (ctx->want_fold && ctx->ref_fold && mode == SR_MODE_LOSS && nt > 0 && fold_n_terms > 0) {
-    // rows a position's store covers under either kernel's grid (row blocks x rows: >= the view)
-    auto cover = [&](int Rc, int depth_c, int64_t* rb_rows) {
-      const Grid gg = make_grid<T>(n_eval, nt, Rc, W, nfk, depth_c, 0, ds->w != nullptr, ctx->tree_group, mrb);
-      *rb_rows = int64_t(gg.tiles) * 64 * Rc;
-      return int64_t(gg.n_row_blocks) * *rb_rows;
-    };
-    int64_t rbr = 0, rbv = 0;
-    int64_t pos_rows = cover(R, 1, &rbr);
-    if (Rv > 0) pos_rows = std::max(pos_rows, cover(Rv, 0, &rbv));
-    fold_slot_rows = std::max(rbr, rbv);
-    const bool fold_mode_builds = tier == SR_TIER_BASIC ? (R == 8 && (Rv == 0 || Rv == 16)) : R == 4;
-    int64_t max_shard = n_eval;
-    if (shard)
-      for (size_t r = 0; r + 1 < ds->shard_offs.size(); ++r) max_shard = std::max(max_shard, ds->shard_offs[r + 1] - ds->shard_offs[r]);
-    // Float64: only with stored losses (no FOLD build), decided on the largest shard so every rank agrees
-    const bool f64_off = sizeof(T) == 8 && double(nt) * double(pos_rows) * double(max_shard) / double(n_eval) *
-                                               double(sizeof(T)) > double(ctx->fold_store_mb) * 1048576.0;
-    // segments (row blocks) past fold_seg_max rows on the largest shard: no fold (a slow segment's rows
-    // are kept whole).  The launch above already takes enough row blocks for fold_seg_max (up to 16,384
-    // blocks); decided on that grid whatever max_row_blocks says, so the knob never changes a result.
-    int64_t rb_big = 0;
-    {
-      const Grid gb = make_grid<T>(max_shard, nt, R, W, nfk, 1, 0, ds->w != nullptr, ctx->tree_group,
-                                   std::max<int64_t>(512, (max_shard + ctx->fold_seg_max - 1) / std::max<int64_t>(1, ctx->fold_seg_max)));
-      rb_big = int64_t(gb.tiles) * 64 * R;
+  int bind_buffers() {
+    s = ctx->stream;
+    img = sr_prog_image(total_nodes, nt, sizeof(SrIns<T>), multi ? size_t(views->n_views) : 0);
+    SR_HIP_CHECK(ctx->prog.ensure(img.bytes));
+    SR_HIP_CHECK(ctx->h_prog.ensure(img.bytes, s, ctx->stream2));
+    dprog = ctx->prog.as<char>();
+    ctx->d_code = dprog;
+    ctx->d_off = reinterpret_cast<uint32_t*>(dprog + img.o_off);
+    ctx->d_bad = reinterpret_cast<uint8_t*>(dprog + img.o_bad);
+    ctx->d_perm = reinterpret_cast<uint32_t*>(dprog + img.o_perm);
+    ctx->d_end = reinterpret_cast<uint32_t*>(dprog + img.o_end);
+    n_part = size_t(nt) * size_t(n_rb);
+    SR_HIP_CHECK(ctx->part_sum.ensure(n_part * sizeof(double) + 8));
+    SR_HIP_CHECK(ctx->part_flag.ensure(n_part * sizeof(uint32_t) + 4));
+    if (mode == SR_MODE_LOSS && ctx->fused_reduce > 0 && size_t(nt) * sizeof(uint32_t) + 4 > ctx->group_cnt.cap) {
+      SR_HIP_CHECK(hipStreamSynchronize(s));  // (the second stream runs only inside a call)
+      SR_HIP_CHECK(ctx->group_cnt.ensure(size_t(nt) * sizeof(uint32_t) + 4));
+      SR_HIP_CHECK(hipMemset(ctx->group_cnt.p, 0, ctx->group_cnt.cap));
     }
-    // folds longer than fold_rows_max (2^24) keep the f64 sum: past ~2^23 rows the reference's Float32
-    // fold stalls (a loss below half an ulp of the running sum adds nothing; C4's 2^26 rows: up to 50 %
-    // below the exact mean) and drifts out of every window the f64 prefix gives the plan, so the walks
-    // fail and the fallback's prediction pass takes the call (C4 folded: 26.6k trees, 37.7 s a step)
-    const int64_t fold_len = shard ? n_total : n_eval;
-    if (f64_off || rb_big > ctx->fold_seg_max || fold_len > ctx->fold_rows_max) {
-    } else if (double(nt) * double(pos_rows) * double(sizeof(T)) <= double(ctx->fold_store_mb) * 1048576.0) {
-      fold_path = 1;
-      SR_HIP_CHECK(ctx->fold_store.ensure(size_t(nt) * size_t(pos_rows) * sizeof(T)));
-    } else if (sizeof(T) == 4 && fold_mode_builds) {
-      fold_path = 2;
-      // (slots for ~24 slow segments per tree — C2 averages 10; a handful of trees over many row blocks
-      //  can need more each: at least 1,024 — up to fold_slot_mb, which caps the call's slots whatever an
-      //  earlier call left allocated: the buffer only ever grows)
-      fold_slots = std::max<int64_t>(1, ctx->fold_slot_mb * 1048576 / (fold_slot_rows * int64_t(sizeof(T))));
-      const int64_t slots = std::min<int64_t>(std::max<int64_t>(int64_t(nt) * 24, 1024), fold_slots);
-      SR_HIP_CHECK(ctx->fold_store.ensure(size_t(slots) * size_t(fold_slot_rows) * sizeof(T)));
-      SR_HIP_CHECK(ctx->fold_ctl.ensure(64));
-      // the call's slot counter, and its (tree, block) pairs taken from the candidates / left to the FOLD pass
-      SR_HIP_CHECK(hipMemsetAsync(ctx->fold_ctl.p, 0, 4 * sizeof(int), s));
-    }
-    if (fold_path && ctx->fold_stats) {
-      SR_HIP_CHECK(ctx->fold_dbg.ensure(size_t(nt) * sizeof(int4) + 16));
-      SR_HIP_CHECK(hipMemsetAsync(ctx->fold_dbg.p, 0, size_t(nt) * sizeof(int4), s));
-    }
-    if (fold_path) {
-      SR_HIP_CHECK(ctx->fold_code.ensure(n_part * sizeof(int32_t) + 4));
-      SR_HIP_CHECK(ctx->fold_tab.ensure(n_part * sizeof(typename SrFoldTab<T>::Pair) + 16));
-      SR_HIP_CHECK(ctx->fold_sq.ensure(n_part * sizeof(int32_t) + 4));
-      SR_HIP_CHECK(ctx->fold_tab2.ensure(n_part * sizeof(typename SrFoldTab<T>::Pair) + 16));
-    }
+    return SR_OK;
   }
-  // the candidate-composing loss launch (sr_ctx::fold_single_pass): plain calls only
-  const bool fold_cand = fold_path == 2 && ctx->fold_single_pass && sizeof(T) == 4 && tier == SR_TIER_BASIC &&
-                         !gather && !multi && !shard && ctx->param == nullptr && n_rb > 1;
-  if (fold_cand) SR_HIP_CHECK(ctx->fold_cand.ensure(n_part * sizeof(int4) + 16));
-  if (!ctx->internal_pass) {  // (the fallback's prediction passes leave the call's record alone)
-    ctx->fold_path_last = fold_path;
-    ctx->fold_timed_last = false;
-    ctx->fold_cand_read = fold_path != 2;
-    ctx->n_cand_taken_last = ctx->n_cand_rerun_last = 0;
-  }
-  // {Σ loss | flags | the fold's values | their status}, one allocation (one DMA back)
-  ctx->outs_flag_off = align256(size_t(nt) * sizeof(double) + 8);
-  ctx->outs_fval_off = align256(ctx->outs_flag_off + size_t(nt) * sizeof(uint32_t) + 4);
-  ctx->outs_fst_off = align256(ctx->outs_fval_off + size_t(nt) * sizeof(T) + 8);
-  const size_t outs_bytes = ctx->outs_fst_off + size_t(nt) * sizeof(int32_t) + 4;
-  ctx->outs_bytes_all = outs_bytes;
-  SR_HIP_CHECK(ctx->outs.ensure(outs_bytes));
-  // latency path (see host_io): results written to pinned host memory, programs read from it
-  const bool small_call = n_chunks == 1 && mode == SR_MODE_LOSS;
-  // (under the in-order fold the plan reads the call's flags and partials on the device; a stored-loss
-  // fold of one row block of <= 256 rows — fold_tiny, the walk alone — reads and writes pinned memory)
-  const bool fold_small = fold_path == 1 && n_rb == 1 && n_eval <= 256;
-  const bool host_out = small_call && ctx->host_io >= 1 && ctx->want_host_out && (fold_path == 0 || fold_small);
-  // (other stored-loss folds of a small call: Σ and flags stay on the device for the pair kernel, and the
-  //  walk copies them to pinned memory beside the fold's values — no copy back, SrFoldWho::msum)
-  const bool fold_mirror = small_call && ctx->host_io >= 1 && ctx->want_host_out && fold_path == 1 && !fold_small &&
-                           !shard;
-  if (host_out || fold_mirror) SR_HIP_CHECK(ctx->h_outs.ensure(outs_bytes, s, ctx->stream2));
-  ctx->outs_on_host = host_out || fold_mirror;
-  const bool host_red = host_out && ctx->host_reduce > 0 && !multi && n_rb > 1 && int64_t(n_part) <= ctx->host_reduce;
-  ctx->host_reductions.clear();
-  ctx->host_red_rb = n_rb;
-  if (host_red) SR_HIP_CHECK(ctx->h_part.ensure(n_part * (sizeof(double) + sizeof(uint32_t)) + 16, s, ctx->stream2));
-  ctx->d_out_sum = reinterpret_cast<double*>(host_out ? ctx->h_outs.as<char>() : ctx->outs.as<char>());
-  ctx->d_out_flag = reinterpret_cast<uint32_t*>((host_out ? ctx->h_outs.as<char>() : ctx->outs.as<char>()) +
-                                                ctx->outs_flag_off);
-  if (mode == SR_MODE_PRED) SR_HIP_CHECK(ctx->pred.ensure(size_t(nt) * size_t(n_eval) * sizeof(T) + 16));
-  const bool use_hint = ctx->dead_hints && mode == SR_MODE_LOSS && n_rb > 1;  // (hints are per position)
-  if (use_hint) {
-    // epoch-tagged hints: each call marks dead positions with its own epoch, so the array needs a
-    // reset only when (re)allocated or when the epoch counter wraps
-    // (a reallocation is detected by the capacity, not the address: the allocator may hand back the
-    // freed address for the larger buffer, whose new part then holds stale words — possibly equal to
-    // this call's epoch, which would mark live trees dead)
-    const size_t cap_before = ctx->hint.cap;
-    const size_t hint_bytes = size_t(nt) * sizeof(uint32_t) + 4;
-    if (ctx->debug_hint_regrow && hint_bytes > ctx->hint.cap) {
-      // (tests: sr_set_tuning "debug_hint_regrow") the array grows IN PLACE, at the same address, its
-      // new words holding the epoch the next call would use without a reset — the conditions of the
-      // round-3 stale-hint bug (a reallocation that got the freed address back); only the capacity
-      // check below catches it
-      constexpr size_t kReserve = size_t(64) << 20;
-      if (hint_bytes + hint_bytes / 4 > kReserve) return set_error(SR_ERR_INVALID_ARG, "debug_hint_regrow: batch too large");
-      if (ctx->hint_reserve == nullptr) SR_HIP_CHECK(hipMalloc(&ctx->hint_reserve, kReserve));
-      if (ctx->hint.p != ctx->hint_reserve) {
-        ctx->hint.release();
-        ctx->hint.p = ctx->hint_reserve;
-      }
-      // (word-aligned: an earlier ordinary allocation may have left an odd capacity)
-      const size_t from = (cap_before + 3) & ~size_t(3);
-      const size_t want = (hint_bytes + hint_bytes / 4 + 255) & ~size_t(255);
-      SR_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(static_cast<char*>(ctx->hint.p) + from),
-                                     int(ctx->hint_epoch + 1), (want - from) / 4, s));
-      ctx->hint.cap = want;
-    } else {
-      if (ctx->hint.p == ctx->hint_reserve && ctx->hint_reserve != nullptr) {  // (leaving the debug mode)
-        ctx->hint.p = nullptr;
-        ctx->hint.cap = 0;
-      }
-      SR_HIP_CHECK(ctx->hint.ensure(hint_bytes));
-    }
-    if (ctx->hint.cap != cap_before || ctx->hint_epoch == 0xffffffffu) {
-      SR_HIP_CHECK(hipMemsetAsync(ctx->hint.p, 0, ctx->hint.cap, s));
-      ctx->hint_epoch = 0;
-    }
-    ++ctx->hint_epoch;
-  }
-  // dead-tree probe: the first kProbeTiles row tiles of the view, hints only (scratch partials)
-  const bool use_probe = use_hint && ctx->probe && n_rb >= 16 && !multi;  // (per chunk: its grid has >= 16 row blocks)
-  if (use_probe) {
-    SR_HIP_CHECK(ctx->probe_sum.ensure(size_t(nt) * kProbeTiles * sizeof(double) + 8));
-    SR_HIP_CHECK(ctx->probe_flag.ensure(size_t(nt) * kProbeTiles * sizeof(uint32_t) + 4));
-  }
-  if (gather) {
-    for (int64_t i = 0; i < n_rows_up; ++i)
-      if (row_idx[i] < 0 || row_idx[i] >= ds->n)
-        return set_error(SR_ERR_INVALID_ARG, "row index " + std::to_string(row_idx[i]) + " out of range");
-    SR_HIP_CHECK(ctx->row_idx.ensure(size_t(n_rows_up) * sizeof(int64_t)));
-  }
-  if (multi)
-    for (int64_t t = 0; t < nt; ++t)
-      if (views->tree_view[t] < 0 || views->tree_view[t] >= views->n_views)
-        return set_error(SR_ERR_INVALID_ARG, "tree " + std::to_string(t) + ": view index out of range");
 
-  prog->code.clear();
-  prog->offsets.assign(size_t(nt) + 1, 0);
-  prog->static_bad.assign(size_t(nt), 0);
-  prog->n_checks.assign(size_t(nt), 0);
-  prog->max_depth = 0;
-  prog->tier = tier;
-  prog->max_checks = 0;
-  prog->total_nodes = 0;
-  prog->total_ops = 0;
-  char* const hprog = ctx->h_prog.as<char>();
-  SrIns<T>* h_code = reinterpret_cast<SrIns<T>*>(hprog);
-  uint32_t* h_off = reinterpret_cast<uint32_t*>(hprog + o_off);
-  uint8_t* h_bad = reinterpret_cast<uint8_t*>(hprog + o_bad);
-  uint32_t* h_perm = reinterpret_cast<uint32_t*>(hprog + o_perm);
-  ctx->h_bad_last = h_bad;
-  ctx->h_perm_last = h_perm;
-  uint32_t* h_end = reinterpret_cast<uint32_t*>(hprog + o_end);
-  ctx->n_chunks_last = 0;
-  ctx->derived_last = false;
-  ctx->n_derived_last = 0;
-  ctx->timed_last = ctx->timing != 0;
-  if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_start, s));
-  if (gather)
-    SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, row_idx, size_t(n_rows_up) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  if (parametric && nt > 0 && p_stride > 0)  // (ahead of the chunks' join: both streams see the table)
-    SR_HIP_CHECK(hipMemcpyAsync(ctx->ptab.p, ctx->h_ptab.p, size_t(nt) * size_t(p_stride) * sizeof(T), hipMemcpyHostToDevice, s));
+  // the reference's in-order loss fold of every complete tree (sr_ctx::ref_fold): the path (sr_fold_plan)
+  // and its buffers
+  // (a row-sharded call: the global rows and every shard's weights; its ranks fold or not together —
+  //  the choice depends on the largest shard's rows, known to every rank)
+  int plan_fold() {
+    fold_n_terms = shard ? ((ds->w && ds->shard_w_min < 0.0) ? 0 : n_total) : fold_terms(ds, n_eval);
+    if (shard) ctx->fold_job.reset();
+    if (ctx->want_fold && ctx->ref_fold && mode == SR_MODE_LOSS && nt > 0 && fold_n_terms > 0) {
+      FoldPlanIn in;
+      in.nt = nt;
+      in.n_eval = n_eval;
+      in.max_shard = shard ? sr_max_shard_rows(ds->shard_offs, n_eval) : n_eval;
+      in.fold_len = shard ? n_total : n_eval;
+      in.elem_size = int(sizeof(T));
+      in.tier = tier;
+      in.R = R;
+      in.Rv = Rv;
+      in.fold_store_mb = ctx->fold_store_mb;
+      in.fold_slot_mb = ctx->fold_slot_mb;
+      in.fold_seg_max = ctx->fold_seg_max;
+      in.fold_rows_max = ctx->fold_rows_max;
+      in.g_ls = g_ls;
+      in.g_vs = g_vs;
+      // NOT the call's spec: the largest shard's rows, and a row-block bound that follows fold_seg_max
+      // whatever max_row_blocks says
+      in.g_big = gs.over(in.max_shard, std::max<int64_t>(512, (in.max_shard + ctx->fold_seg_max - 1) /
+                                                                     std::max<int64_t>(1, ctx->fold_seg_max)))
+                     .grid(nt, R, 1);
+      fold = sr_fold_plan(in);
+      if (fold.path == 1) {
+        SR_HIP_CHECK(ctx->fold_store.ensure(size_t(nt) * size_t(fold.pos_rows) * sizeof(T)));
+      } else if (fold.path == 2) {
+        SR_HIP_CHECK(ctx->fold_store.ensure(size_t(fold.slots) * size_t(fold.slot_rows) * sizeof(T)));
+        SR_HIP_CHECK(ctx->fold_ctl.ensure(64));
+        // the call's slot counter, and its (tree, block) pairs taken from the candidates / left to the FOLD pass
+        SR_HIP_CHECK(hipMemsetAsync(ctx->fold_ctl.p, 0, 4 * sizeof(int), s));
+      }
+      if (fold.path && ctx->fold_stats) {
+        SR_HIP_CHECK(ctx->fold_dbg.ensure(size_t(nt) * sizeof(int4) + 16));
+        SR_HIP_CHECK(hipMemsetAsync(ctx->fold_dbg.p, 0, size_t(nt) * sizeof(int4), s));
+      }
+      if (fold.path) {
+        SR_HIP_CHECK(ctx->fold_code.ensure(n_part * sizeof(int32_t) + 4));
+        SR_HIP_CHECK(ctx->fold_tab.ensure(n_part * sizeof(typename SrFoldTab<T>::Pair) + 16));
+        SR_HIP_CHECK(ctx->fold_sq.ensure(n_part * sizeof(int32_t) + 4));
+        SR_HIP_CHECK(ctx->fold_tab2.ensure(n_part * sizeof(typename SrFoldTab<T>::Pair) + 16));
+      }
+    }
+    // the candidate-composing loss launch (sr_ctx::fold_single_pass): plain calls only
+    fold_cand = fold.path == 2 && ctx->fold_single_pass && sizeof(T) == 4 && tier == SR_TIER_BASIC && !gather &&
+                !multi && !shard && ctx->param == nullptr && n_rb > 1;
+    if (fold_cand) SR_HIP_CHECK(ctx->fold_cand.ensure(n_part * sizeof(int4) + 16));
+    if (!ctx->internal_pass) {  // (the fallback's prediction passes leave the call's record alone)
+      ctx->fold_path_last = fold.path;
+      ctx->fold_timed_last = false;
+      ctx->fold_cand_read = fold.path != 2;
+      ctx->n_cand_taken_last = ctx->n_cand_rerun_last = 0;
+    }
+    return SR_OK;
+  }
+
+  // The call's results: {Σ loss | flags | the fold's values | their status}, one allocation (one DMA back),
+  // on the device or — the latency path — in pinned host memory; the PRED rows.
+  int bind_outputs() {
+    ctx->outs_flag_off = sr_align256(size_t(nt) * sizeof(double) + 8);
+    ctx->outs_fval_off = sr_align256(ctx->outs_flag_off + size_t(nt) * sizeof(uint32_t) + 4);
+    ctx->outs_fst_off = sr_align256(ctx->outs_fval_off + size_t(nt) * sizeof(T) + 8);
+    const size_t outs_bytes = ctx->outs_fst_off + size_t(nt) * sizeof(int32_t) + 4;
+    ctx->outs_bytes_all = outs_bytes;
+    SR_HIP_CHECK(ctx->outs.ensure(outs_bytes));
+    // latency path (see host_io): results written to pinned host memory, programs read from it
+    const bool small_call = n_chunks == 1 && mode == SR_MODE_LOSS;
+    // (under the in-order fold the plan reads the call's flags and partials on the device; a stored-loss
+    // fold of one row block of <= 256 rows — fold_tiny, the walk alone — reads and writes pinned memory)
+    const bool fold_small = fold.path == 1 && n_rb == 1 && n_eval <= 256;
+    host_out = small_call && ctx->host_io >= 1 && ctx->want_host_out && (fold.path == 0 || fold_small);
+    // (other stored-loss folds of a small call: Σ and flags stay on the device for the pair kernel, and the
+    //  walk copies them to pinned memory beside the fold's values — no copy back, SrFoldWho::msum)
+    fold_mirror = small_call && ctx->host_io >= 1 && ctx->want_host_out && fold.path == 1 && !fold_small && !shard;
+    if (host_out || fold_mirror) SR_HIP_CHECK(ctx->h_outs.ensure(outs_bytes, s, ctx->stream2));
+    ctx->outs_on_host = host_out || fold_mirror;
+    host_red = host_out && ctx->host_reduce > 0 && !multi && n_rb > 1 && int64_t(n_part) <= ctx->host_reduce;
+    ctx->host_reductions.clear();
+    ctx->host_red_rb = n_rb;
+    if (host_red) SR_HIP_CHECK(ctx->h_part.ensure(n_part * (sizeof(double) + sizeof(uint32_t)) + 16, s, ctx->stream2));
+    char* const sums_base = host_out ? ctx->h_outs.as<char>() : ctx->outs.as<char>();
+    ctx->d_out_sum = reinterpret_cast<double*>(sums_base);
+    ctx->d_out_flag = reinterpret_cast<uint32_t*>(sums_base + ctx->outs_flag_off);
+    if (mode == SR_MODE_PRED) SR_HIP_CHECK(ctx->pred.ensure(size_t(nt) * size_t(n_eval) * sizeof(T) + 16));
+    return SR_OK;
+  }
+
+  // Dead-tree hints (one word per launch position) and the probe's scratch partials.
+  int prepare_hints() {
+    use_hint = ctx->dead_hints && mode == SR_MODE_LOSS && n_rb > 1;  // (hints are per position)
+    if (use_hint) {
+      // epoch-tagged hints: each call marks dead positions with its own epoch, so the array needs a
+      // reset only when (re)allocated or when the epoch counter wraps
+      // (a reallocation is detected by the capacity, not the address: the allocator may hand back the
+      // freed address for the larger buffer, whose new part then holds stale words — possibly equal to
+      // this call's epoch, which would mark live trees dead)
+      const size_t cap_before = ctx->hint.cap;
+      const size_t hint_bytes = size_t(nt) * sizeof(uint32_t) + 4;
+      if (ctx->debug_hint_regrow && hint_bytes > ctx->hint.cap) {
+        // (tests: sr_set_tuning "debug_hint_regrow") the array grows IN PLACE, at the same address, its
+        // new words holding the epoch the next call would use without a reset — the conditions of the
+        // round-3 stale-hint bug (a reallocation that got the freed address back); only the capacity
+        // check below catches it
+        constexpr size_t kReserve = size_t(64) << 20;
+        if (hint_bytes + hint_bytes / 4 > kReserve) return set_error(SR_ERR_INVALID_ARG, "debug_hint_regrow: batch too large");
+        if (ctx->hint_reserve == nullptr) SR_HIP_CHECK(hipMalloc(&ctx->hint_reserve, kReserve));
+        if (ctx->hint.p != ctx->hint_reserve) {
+          ctx->hint.release();
+          ctx->hint.p = ctx->hint_reserve;
+        }
+        // (word-aligned: an earlier ordinary allocation may have left an odd capacity)
+        const size_t from = (cap_before + 3) & ~size_t(3);
+        const size_t want = (hint_bytes + hint_bytes / 4 + 255) & ~size_t(255);
+        SR_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(static_cast<char*>(ctx->hint.p) + from),
+                                       int(ctx->hint_epoch + 1), (want - from) / 4, s));
+        ctx->hint.cap = want;
+      } else {
+        if (ctx->hint.p == ctx->hint_reserve && ctx->hint_reserve != nullptr) {  // (leaving the debug mode)
+          ctx->hint.p = nullptr;
+          ctx->hint.cap = 0;
+        }
+        SR_HIP_CHECK(ctx->hint.ensure(hint_bytes));
+      }
+      if (ctx->hint.cap != cap_before || ctx->hint_epoch == 0xffffffffu) {
+        SR_HIP_CHECK(hipMemsetAsync(ctx->hint.p, 0, ctx->hint.cap, s));
+        ctx->hint_epoch = 0;
+      }
+      ++ctx->hint_epoch;
+    }
+    // dead-tree probe: the first kProbeTiles row tiles of the view, hints only (scratch partials)
+    use_probe = use_hint && ctx->probe && n_rb >= 16 && !multi;  // (per chunk: its grid has >= 16 row blocks)
+    if (use_probe) {
+      SR_HIP_CHECK(ctx->probe_sum.ensure(size_t(nt) * kProbeTiles * sizeof(double) + 8));
+      SR_HIP_CHECK(ctx->probe_flag.ensure(size_t(nt) * kProbeTiles * sizeof(uint32_t) + 4));
+    }
+    return SR_OK;
+  }
+
+  // The view's row indices and the views' tree map checked; the merged summary and the call's record reset;
+  // the staging pointers bound; the call's first uploads (row indices, a parametric call's table).
+  int begin_programs() {
+    if (gather) {
+      for (int64_t i = 0; i < n_rows_up; ++i)
+        if (row_idx[i] < 0 || row_idx[i] >= ds->n)
+          return set_error(SR_ERR_INVALID_ARG, "row index " + std::to_string(row_idx[i]) + " out of range");
+      SR_HIP_CHECK(ctx->row_idx.ensure(size_t(n_rows_up) * sizeof(int64_t)));
+    }
+    if (multi)
+      for (int64_t t = 0; t < nt; ++t)
+        if (views->tree_view[t] < 0 || views->tree_view[t] >= views->n_views)
+          return set_error(SR_ERR_INVALID_ARG, "tree " + std::to_string(t) + ": view index out of range");
+
+    prog->code.clear();
+    prog->offsets.assign(size_t(nt) + 1, 0);
+    prog->static_bad.assign(size_t(nt), 0);
+    prog->n_checks.assign(size_t(nt), 0);
+    prog->max_depth = 0;
+    prog->tier = tier;
+    prog->max_checks = 0;
+    prog->total_nodes = 0;
+    prog->total_ops = 0;
+    hprog = ctx->h_prog.as<char>();
+    h_code = reinterpret_cast<SrIns<T>*>(hprog);
+    h_off = reinterpret_cast<uint32_t*>(hprog + img.o_off);
+    h_bad = reinterpret_cast<uint8_t*>(hprog + img.o_bad);
+    h_perm = reinterpret_cast<uint32_t*>(hprog + img.o_perm);
+    ctx->h_bad_last = h_bad;
+    ctx->h_perm_last = h_perm;
+    h_end = reinterpret_cast<uint32_t*>(hprog + img.o_end);
+    ctx->n_chunks_last = 0;
+    ctx->derived_last = false;
+    ctx->n_derived_last = 0;
+    ctx->timed_last = ctx->timing != 0;
+    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_start, s));
+    if (gather)
+      SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, row_idx, size_t(n_rows_up) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (parametric && nt > 0 && p_stride > 0)  // (ahead of the chunks' join: both streams see the table)
+      SR_HIP_CHECK(hipMemcpyAsync(ctx->ptab.p, ctx->h_ptab.p, size_t(nt) * size_t(p_stride) * sizeof(T), hipMemcpyHostToDevice, s));
+    return SR_OK;
+  }
+
   // derived columns (LOAD_DERIVED): for the BASIC-tier deferred-check loss kernels over many rows,
   // every unary(feature) node of a transcendental shared by several trees is evaluated once for the
   // call.  Chosen from a sample of the batch; not when the data itself needs tracked feature loads.
-  std::vector<int16_t> dmap;
-  SrDerivedSpec spec{};
-  const int64_t dld = (n_eval + kRowAlign - 1) / kRowAlign * kRowAlign;
-  // (row-sharded calls pass `shard`: the choice then depends only on the trees and on statistics of
-  // every shard, so all ranks compile the same programs and number their checked arrays alike)
-  const double max_abs_x = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
-  const int64_t derived_rows = shard ? shard->min_rows : n_eval;
-  // (and only for calls with enough work: the column pass is one more launch, which a search's small
-  // calls — tens of trees x 1e5 rows — would pay in latency for nothing)
-  if (allow_derived && ctx->derived && mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && derived_rows >= kDerivedMinRows &&
-      nt >= 64 && double(nt) * double(derived_rows) >= kDerivedMinWork &&
-      max_abs_x < double(T(t_max<T>() / (2.0 * double(n_total > 0 ? n_total : 1))))) {  // (track_x off)
-    choose_derived(*trees, ctx->opsets[opset_id], ds->nf, &spec, &dmap);
-    if (spec.n > 0) {
-      SR_HIP_CHECK(ctx->derived_cols.ensure(size_t(spec.n) * size_t(dld) * sizeof(T)));
-      if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_d0, s));
-      SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(ds->X), ds->ld, gather ? ctx->row_idx.as<int64_t>() : nullptr,
-                                        n_eval, dld, spec, ctx->derived_cols.as<T>(), dld, s));
-      if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_d1, s));
-      ctx->derived_last = true;
-      ctx->n_derived_last = spec.n;
-    } else {
-      dmap.clear();
+  int launch_derived() {
+    dld = (n_eval + kRowAlign - 1) / kRowAlign * kRowAlign;
+    // (row-sharded calls pass `shard`: the choice then depends only on the trees and on statistics of
+    // every shard, so all ranks compile the same programs and number their checked arrays alike)
+    max_abs_x = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
+    const int64_t derived_rows = shard ? shard->min_rows : n_eval;
+    // (and only for calls with enough work: the column pass is one more launch, which a search's small
+    // calls — tens of trees x 1e5 rows — would pay in latency for nothing)
+    if (allow_derived && ctx->derived && mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && derived_rows >= kDerivedMinRows &&
+        nt >= 64 && double(nt) * double(derived_rows) >= kDerivedMinWork && max_abs_x < double(tbig())) {  // (track_x off)
+      choose_derived(*trees, ctx->opsets[opset_id], ds->nf, &spec, &dmap);
+      if (spec.n > 0) {
+        SR_HIP_CHECK(ctx->derived_cols.ensure(size_t(spec.n) * size_t(dld) * sizeof(T)));
+        if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_d0, s));
+        SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(ds->X), ds->ld, gather ? ctx->row_idx.as<int64_t>() : nullptr,
+                                          n_eval, dld, spec, ctx->derived_cols.as<T>(), dld, s));
+        if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_d1, s));
+        ctx->derived_last = true;
+        ctx->n_derived_last = spec.n;
+      } else {
+        dmap.clear();
+      }
     }
-  }
-  // the probe over the dataset's stress rows (full views only: a gathered view's rows are its own);
-  // its LOAD_DERIVED nodes read columns computed over those rows
-  const bool stress_probe = use_probe && !gather && ds->probe_rows != nullptr && ctx->stress_probe;
-  if (stress_probe && !dmap.empty()) {
-    SR_HIP_CHECK(ctx->probe_derived.ensure(size_t(spec.n) * size_t(kProbeRows) * sizeof(T)));
-    SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(ds->X), ds->ld, static_cast<const int64_t*>(ds->probe_rows),
-                                      ds->n_probe, kProbeRows, spec, ctx->probe_derived.as<T>(), kProbeRows, s));
-  }
-  if (n_chunks > 1) {  // odd chunks run on the second stream, after the shared setup above
-    SR_HIP_CHECK(ctx->need_stream2());
-    SR_HIP_CHECK(hipEventRecord(ctx->ev_join, s));
-    SR_HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->ev_join, 0));
+    // the probe over the dataset's stress rows (full views only: a gathered view's rows are its own);
+    // its LOAD_DERIVED nodes read columns computed over those rows
+    stress_probe = use_probe && !gather && ds->probe_rows != nullptr && ctx->stress_probe;
+    if (stress_probe && !dmap.empty()) {
+      SR_HIP_CHECK(ctx->probe_derived.ensure(size_t(spec.n) * size_t(kProbeRows) * sizeof(T)));
+      SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(ds->X), ds->ld, static_cast<const int64_t*>(ds->probe_rows),
+                                        ds->n_probe, kProbeRows, spec, ctx->probe_derived.as<T>(), kProbeRows, s));
+    }
+    return SR_OK;
   }
 
+  // The second stream joins the shared setup; the fold's launch facts.
   // the fold's launches per chunk: every launch of the chunk, then its plan / tables / FOLD pass / walk
-  FoldJob<T> fjob;  // (the regions of the chunk being launched; a row-sharded call's: all of them, kept)
-  fjob.path = fold_path;
-  fjob.tier = tier;
-  fjob.gather = gather;
-  fjob.n_eval = n_eval;
-  fjob.n_rb = n_rb;
-  fjob.slot_rows = fold_slot_rows;
-  fjob.n_terms = fold_n_terms;
-  fjob.delta = std::ldexp(1.0, -ctx->fold_delta_log2);
-  // stored losses on one GPU: the pair kernel reduces the partials itself (one launch fewer a call;
-  // SR_AMD_FOLD_REDUCE=0: the reduce launch)
-  fjob.fuse_reduce = fold_path == 1 && !shard && mode == SR_MODE_LOSS && ctx->fold_reduce;
-  fjob.slot_cap = fold_path == 2 ? int(std::min<int64_t>({int64_t(INT_MAX / 2), fold_slots,
-                                                          int64_t(ctx->fold_store.cap / (size_t(fold_slot_rows) * sizeof(T)))}))
-                                 : 0;
-  size_t fold_store_at = 0;  // (stored losses: the regions one after another, [position][n_rb x rb rows])
-  char* const outs_base = (host_out || fold_mirror) ? ctx->h_outs.as<char>() : ctx->outs.as<char>();
-  T* const d_fval = reinterpret_cast<T*>(outs_base + ctx->outs_fval_off);
-  int32_t* const d_fst = reinterpret_cast<int32_t*>(outs_base + ctx->outs_fst_off);
-  uint32_t code_base = 0;
-  static const bool phase_debug = std::getenv("SR_AMD_PHASE_DEBUG") != nullptr;  // (latency analysis)
-  const auto t_pre = std::chrono::steady_clock::now();
-  Grid glast = g0;
-  std::string err;
-  for (int c = 0; c < n_chunks && nt > 0; ++c) {
-    // two chunks: a small first one (1/6) runs while the host compiles the rest, so the exposed
-    // compile time is the small chunk's; more chunks: equal pieces
-    auto bound = [&](int k) -> int64_t {
-      if (k <= 0) return 0;
-      if (k >= n_chunks) return nt;
-      return n_chunks == 2 ? nt / ctx->first_chunk : nt * k / n_chunks;
-    };
-    const int64_t t0 = bound(c), t1 = bound(c + 1), nc = t1 - t0;
-    uint32_t max_nodes = 1;  // the chunk's largest tree (bounds the untracked values: SR_TRACK_LITE)
-    for (int64_t t = t0; t < t1; ++t)
-      max_nodes = std::max<uint32_t>(max_nodes, uint32_t(trees->offsets[t + 1] - trees->offsets[t]));
+  int begin_chunks() {
+    if (n_chunks > 1) {  // odd chunks run on the second stream, after the shared setup above
+      SR_HIP_CHECK(ctx->need_stream2());
+      SR_HIP_CHECK(hipEventRecord(ctx->ev_join, s));
+      SR_HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->ev_join, 0));
+    }
+    fjob.path = fold.path;
+    fjob.tier = tier;
+    fjob.gather = gather;
+    fjob.n_eval = n_eval;
+    fjob.n_rb = n_rb;
+    fjob.slot_rows = fold.slot_rows;
+    fjob.n_terms = fold_n_terms;
+    fjob.delta = std::ldexp(1.0, -ctx->fold_delta_log2);
+    // stored losses on one GPU: the pair kernel reduces the partials itself (one launch fewer a call;
+    // SR_AMD_FOLD_REDUCE=0: the reduce launch)
+    fjob.fuse_reduce = fold.path == 1 && !shard && mode == SR_MODE_LOSS && ctx->fold_reduce;
+    fjob.slot_cap = fold.path == 2
+                        ? int(std::min<int64_t>({int64_t(INT_MAX / 2), fold.slot_budget,
+                                                 int64_t(ctx->fold_store.cap / (size_t(fold.slot_rows) * sizeof(T)))}))
+                        : 0;
+    char* const outs_base = (host_out || fold_mirror) ? ctx->h_outs.as<char>() : ctx->outs.as<char>();
+    d_fval = reinterpret_cast<T*>(outs_base + ctx->outs_fval_off);
+    d_fst = reinterpret_cast<int32_t*>(outs_base + ctx->outs_fst_off);
+    t_pre = std::chrono::steady_clock::now();
+    return SR_OK;
+  }
+
+  // Chunk c's bounds, stream and compiled programs.
+  int compile_chunk(BatchChunk<T>& ch) {
+    static const bool phase_debug = std::getenv("SR_AMD_PHASE_DEBUG") != nullptr;  // (latency analysis)
+    const int64_t t0 = ch.t0 = sr_chunk_bound(ch.c, n_chunks, nt, ctx->first_chunk);
+    const int64_t nc = ch.nc = sr_chunk_bound(ch.c + 1, n_chunks, nt, ctx->first_chunk) - t0;
+    for (int64_t t = t0; t < t0 + nc; ++t)
+      ch.max_nodes = std::max<uint32_t>(ch.max_nodes, uint32_t(trees->offsets[t + 1] - trees->offsets[t]));
     // chunks alternate between two streams: chunk c+1's workgroups fill the GPU while chunk c drains
-    const hipStream_t cs = (c & 1) ? ctx->stream2 : s;
+    ch.cs = (ch.c & 1) ? ctx->stream2 : s;
     sr_tree_batch sub = *trees;
     sub.n_trees = nc;
     sub.offsets = trees->offsets + t0;  // node arrays stay indexed by absolute offsets
-    SrProgramBatch<T> pc;
-    pc.keep_pieces = true;  // (staged below straight from the compile workers' buffers)
+    ch.pc.keep_pieces = true;  // (staged below straight from the compile workers' buffers)
     // (a parametric batch's per-node arrays are indexed by absolute node offsets, like the tree batch's)
     const SrParamNodes pnodes{parametric ? pb->is_parameter : nullptr, parametric ? pb->parameter : nullptr,
                               parametric ? pb->max_parameters : 0};
-    int rc = sr_compile_batch<T>(sub, ctx->opsets[opset_id], n_total, ds->nf, false, &pc, &err,
-                                 dmap.empty() ? nullptr : dmap.data(), parametric ? &pnodes : nullptr);
+    const int rc = sr_compile_batch<T>(sub, ctx->opsets[opset_id], n_total, ds->nf, false, &ch.pc, &err,
+                                       dmap.empty() ? nullptr : dmap.data(), parametric ? &pnodes : nullptr);
     if (rc != SR_OK) {
-      sync_both();  // earlier chunks may still read the staging buffers
       if (rc == SR_ERR_BAD_TREE || rc == SR_ERR_INVALID_ARG) {
         // report the tree index of the whole batch
         const size_t at = err.find("tree ");
@@ -1115,7 +1105,7 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       }
       return set_error(rc, err);
     }
-    if (c == 0) {
+    if (ch.c == 0) {
       if (phase_debug) {
         const auto now = std::chrono::steady_clock::now();
         std::fprintf(stderr, "[sr phase] trees %lld chunks %d: setup %.3f ms, compile of chunk 0 (%lld trees) %.3f ms\n",
@@ -1124,124 +1114,66 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
       }
       ctx->mark_phase(0);
     }
-    const int depth = pc.max_depth > 0 ? pc.max_depth : 1;
-    // Trees whose programs fit the register stack (<= 2 slots: every tree of < 23 nodes, most of the
-    // rest) run on the register-stack kernel; the few deeper ones follow in a second launch of the
-    // LDS-stack kernel over the tail of the launch order.
-    int64_t n_vs = 0;  // launch positions [0, n_vs) -> register-stack kernel
-    if (Rv > 0)
-      for (int64_t i = 0; i < nc; ++i) n_vs += pc.depth[size_t(i)] <= SR_VSTK_SLOTS ? 1 : 0;
-    // stage: code at code_base, offsets made absolute, static_bad, launch order (chunk-local)
-    const size_t ncode = pc.n_code;
-    if (code_base + ncode > code_cap) {
-      sync_both();
-      return set_error(SR_ERR_INVALID_ARG, "program longer than its node count");
-    }
+    ch.depth = ch.pc.max_depth > 0 ? ch.pc.max_depth : 1;
+    ch.ncode = ch.pc.n_code;
+    return SR_OK;
+  }
+
+  // The chunk's launch plan (sr_plan.h) and its staging image: code at code_base, offsets made absolute,
+  // static_bad, launch order (chunk-local), view segments.
+  int order_and_stage(BatchChunk<T>& ch) {
+    const SrProgramBatch<T>& pc = ch.pc;
+    const int64_t t0 = ch.t0, nc = ch.nc;
+    ch.n_vs = sr_count_vstk(pc.depth.data(), nc, Rv > 0);
+    // the chunk's two launches: the register-stack trees, then the deeper ones on the LDS-stack kernel
+    if (ch.n_vs > 0) ch.g_vs = gs.grid(ch.n_vs, Rv, 0);
+    if (ch.n_vs < nc) ch.g_ls = gs.grid(nc - ch.n_vs, R, ch.depth);
+    if (code_base + ch.ncode > img.code_cap) return set_error(SR_ERR_INVALID_ARG, "program longer than its node count");
     std::memcpy(h_bad + t0, pc.static_bad.data(), size_t(nc));
-    {
-      // launch order: register-stack trees first, each class in decreasing estimated cost so every
-      // block's waves get similar work (counting sort: costs are small integers; ties keep order)
-      const std::vector<uint32_t>& cost = pc.cost;
-      const bool sort = ctx->cost_order && nc > 1;
-      uint32_t cmax = 0;
-      if (sort)
-        for (uint32_t v : cost) cmax = v > cmax ? v : cmax;
-      const size_t nkey = size_t(cmax) + 1;
-      // several views: the view first (each view's trees contiguous: its own segment of tree groups)
-      const size_t n_cls = multi ? size_t(views->n_views) : 2;
-      std::vector<uint32_t> start(n_cls * nkey + 1, 0);
-      auto key = [&](int64_t i) -> size_t {
-        const size_t cls = multi ? size_t(views->tree_view[t0 + i])
-                                 : ((Rv > 0 && pc.depth[size_t(i)] > SR_VSTK_SLOTS) ? 1 : 0);
-        return cls * nkey + (sort ? size_t(cmax - cost[size_t(i)]) : 0);
-      };
-      for (int64_t i = 0; i < nc; ++i) ++start[key(i) + 1];
-      for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
-      for (int64_t i = 0; i < nc; ++i) h_perm[t0 + start[key(i)]++] = uint32_t(i);
-      // Deal the cost-ordered trees of each class round-robin over that launch's tree groups (group
-      // g takes ranks g, g + n_groups, ...; each group's positions stay in decreasing cost, so its
-      // waves still get equal work).  Contiguous cost ranks made the first groups' workgroups several
-      // times longer than the last groups' and the launch ended on a tail of heavy workgroups (C2's
-      // complete trees: 4.36 ms with contiguous groups of 128, 3.32 unsorted).
-      if (sort && ctx->balance_groups && !multi) {
-        auto deal = [&](int64_t p0, int64_t np, int Rc, int depth_c) {
-          if (np <= 1) return;
-          const Grid gc = make_grid<T>(n_eval, np, Rc, W, nfk, depth_c, 0, ds->w != nullptr, ctx->tree_group,
-                                       mrb);
-          const int64_t G = gc.G, ng = gc.n_groups;
-          if (ng <= 1) return;
-          std::vector<uint32_t> ranked(h_perm + t0 + p0, h_perm + t0 + p0 + np);
-          int64_t k = 0;
-          for (int64_t j = 0; j < G; ++j)
-            for (int64_t gi = 0; gi < ng; ++gi) {
-              const int64_t size = gi + 1 < ng ? G : np - (ng - 1) * G;
-              if (j < size) h_perm[t0 + p0 + gi * G + j] = ranked[size_t(k++)];
-            }
-        };
-        if (n_vs > 0) deal(0, n_vs, Rv, 0);
-        if (n_vs < nc) deal(n_vs, nc - n_vs, R, depth);
+    uint32_t* const perm = h_perm + t0;
+    sr_launch_order(pc.cost.data(), pc.depth.data(), nc, multi ? views->tree_view + t0 : nullptr,
+                    multi ? views->n_views : 0, ctx->cost_order, ctx->balance_groups, Rv > 0,
+                    GroupShape{ch.g_vs.G, ch.g_vs.n_groups}, GroupShape{ch.g_ls.G, ch.g_ls.n_groups}, perm);
+    uint32_t* const off = h_off + t0;
+    uint32_t* const end = h_end + t0;
+    sr_code_layout(perm, pc.offsets.data(), nc, code_base, off, end);
+    // the copies into the pinned staging buffer: a large chunk's ~2 MB on the compile workers
+    // (single-threaded they sat on the host path between the first chunk's launch and the second's)
+    auto copy = [&](int64_t p0, int64_t p1) {
+      for (int64_t p = p0; p < p1; ++p) {
+        const uint32_t i = perm[p];
+        const uint32_t len = end[i] - off[i];
+        if (len) std::memcpy(h_code + off[i], pc.tree_code(i), size_t(len) * sizeof(SrIns<T>));
       }
-    }
-    {
-      // programs in launch order: a tree group's code is one contiguous span (the kernel's LDS program
-      // cache copies it in one pass); offsets / ends stay indexed by tree
-      uint32_t at = code_base;
-      for (int64_t p = 0; p < nc; ++p) {  // destinations: a prefix over the launch order
-        const uint32_t i = h_perm[t0 + p];
-        const uint32_t len = pc.offsets[size_t(i) + 1] - pc.offsets[size_t(i)];
-        h_off[t0 + i] = at;
-        h_end[t0 + i] = at + len;
-        at += len;
-      }
-      // the copies into the pinned staging buffer: a large chunk's ~2 MB on the compile workers
-      // (single-threaded they sat on the host path between the first chunk's launch and the second's)
-      auto copy = [&](int64_t p0, int64_t p1) {
-        for (int64_t p = p0; p < p1; ++p) {
-          const uint32_t i = h_perm[t0 + p];
-          const uint32_t len = h_end[t0 + i] - h_off[t0 + i];
-          if (len) std::memcpy(h_code + h_off[t0 + i], pc.tree_code(i), size_t(len) * sizeof(SrIns<T>));
-        }
-      };
-      constexpr int64_t kCopyPiece = 512;
-      if (ctx->par_stage && nc >= 4 * kCopyPiece) {
-        sr_parallel_for(int((nc + kCopyPiece - 1) / kCopyPiece), [&](int w) {
-          const int64_t p0 = int64_t(w) * kCopyPiece;
-          copy(p0, std::min<int64_t>(nc, p0 + kCopyPiece));
-        });
-      } else {
-        copy(0, nc);
-      }
-    }
-    // several views: one segment per view present (launch positions in view order), tree groups of the
-    // launch's G, blocks in segment order
-    int n_seg = 0;
-    int64_t seg_blocks = 0;
-    if (multi && nc > 0) {
-      const Grid gm = make_grid<T>(n_eval, nc, R, W, nfk, depth, 0, ds->w != nullptr, ctx->tree_group,
-                                   mrb);
-      SrSegment* hs = reinterpret_cast<SrSegment*>(hprog + o_seg);
-      for (int64_t p = 0; p < nc;) {
-        const int v = views->tree_view[t0 + h_perm[t0 + p]];
-        int64_t q = p;
-        while (q < nc && views->tree_view[t0 + h_perm[t0 + q]] == v) ++q;
-        SrSegment sg{};
-        sg.block0 = int(seg_blocks);
-        sg.pos0 = int(p);
-        sg.n_pos = int(q - p);
-        sg.groups = int((q - p + gm.G - 1) / gm.G);
-        sg.row_off = int64_t(v) * n_idx;
-        hs[n_seg++] = sg;
-        seg_blocks += int64_t(sg.groups) * gm.n_row_blocks;
-        p = q;
-      }
-    }
-    if (n_chunks == 1) {  // the whole staging image (code, offsets, static_bad, order): one DMA
-      const size_t img = multi ? o_seg + size_t(n_seg) * sizeof(SrSegment) : o_end + size_t(nc) * sizeof(uint32_t);
-      SR_HIP_CHECK(hipMemcpyAsync(dprog, hprog, img, hipMemcpyHostToDevice, cs));
+    };
+    constexpr int64_t kCopyPiece = 512;
+    if (ctx->par_stage && nc >= 4 * kCopyPiece) {
+      sr_parallel_for(int((nc + kCopyPiece - 1) / kCopyPiece), [&](int w) {
+        const int64_t p0 = int64_t(w) * kCopyPiece;
+        copy(p0, std::min<int64_t>(nc, p0 + kCopyPiece));
+      });
     } else {
-      if (ncode)
+      copy(0, nc);
+    }
+    // (several views: Rv = 0, so the one launch's grid is g_ls)
+    if (multi && nc > 0)
+      ch.seg_blocks = sr_view_segments(views->tree_view + t0, perm, nc, ch.g_ls.G, ch.g_ls.n_row_blocks, n_idx,
+                                       reinterpret_cast<SrSegment*>(hprog + img.o_seg), &ch.n_seg);
+    return SR_OK;
+  }
+
+  // The chunk's programs to the device, and its part of the merged summary.
+  int upload_chunk(BatchChunk<T>& ch) {
+    const SrProgramBatch<T>& pc = ch.pc;
+    const int64_t t0 = ch.t0, nc = ch.nc;
+    hipStream_t cs = ch.cs;
+    if (n_chunks == 1) {  // the whole staging image (code, offsets, static_bad, order): one DMA
+      const size_t used = multi ? img.o_seg + size_t(ch.n_seg) * sizeof(SrSegment) : img.o_end + size_t(nc) * sizeof(uint32_t);
+      SR_HIP_CHECK(hipMemcpyAsync(dprog, hprog, used, hipMemcpyHostToDevice, cs));
+    } else {
+      if (ch.ncode)
         SR_HIP_CHECK(hipMemcpyAsync(static_cast<SrIns<T>*>(ctx->d_code) + code_base, h_code + code_base,
-                                    ncode * sizeof(SrIns<T>), hipMemcpyHostToDevice, cs));
+                                    ch.ncode * sizeof(SrIns<T>), hipMemcpyHostToDevice, cs));
       SR_HIP_CHECK(hipMemcpyAsync(ctx->d_off + t0, h_off + t0, size_t(nc) * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
       SR_HIP_CHECK(hipMemcpyAsync(ctx->d_end + t0, h_end + t0, size_t(nc) * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
       SR_HIP_CHECK(hipMemcpyAsync(ctx->d_bad + t0, h_bad + t0, size_t(nc), hipMemcpyHostToDevice, cs));
@@ -1255,230 +1187,290 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
     if (pc.max_checks > prog->max_checks) prog->max_checks = pc.max_checks;
     prog->total_nodes += pc.total_nodes;
     prog->total_ops += pc.total_ops;
+    return SR_OK;
+  }
 
-    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_c0[c], cs));  // the chunk's kernel time includes its probe
-    // one launch over launch positions [p0, p0 + np) of the chunk; its partials occupy
-    // [n_rb][np] words from p0 * n_rb (the chunk's region holds n_rb rows for every position)
-    auto launch = [&](int64_t p0, int64_t np, bool vstk) -> int {
-      const int Rc = vstk ? Rv : R;
-      Grid g = make_grid<T>(n_eval, np, Rc, W, nfk, vstk ? 0 : depth, 0, ds->w != nullptr, ctx->tree_group,
-                           mrb);
-      if (g.lds > kLdsMax)
-        return set_error(SR_ERR_TOO_DEEP, "the row tile (" + std::to_string(ds->nf) + " features, " +
-                                              std::to_string(depth) + " stack slots) needs " + std::to_string(g.lds) +
-                                              " bytes of LDS; the limit is 160 KiB");
-      if (g.n_blocks > 0x7fffffff || g.n_row_blocks > n_rb) return set_error(SR_ERR_INVALID_ARG, "grid too large");
-      glast = g;
-      SrEvalArgs<T> a{};
-      a.code = static_cast<const SrIns<T>*>(ctx->d_code);
-      a.offsets = ctx->d_off + t0;
-      a.ends = ctx->d_end + t0;
-      a.perm = ctx->d_perm + t0 + p0;
-      a.hint = use_hint ? ctx->hint.as<uint32_t>() + t0 + p0 : nullptr;
-      a.hint_epoch = ctx->hint_epoch;
-      a.n_trees = int(np);
-      a.trees_per_block = g.G;
-      a.X = static_cast<const T*>(ds->X);
-      a.y = static_cast<const T*>(ds->y);
-      a.w = static_cast<const T*>(ds->w);
-      a.row_idx = gather ? ctx->row_idx.as<int64_t>() : nullptr;
-      a.ld = ds->ld;
-      a.derived = dmap.empty() ? nullptr : ctx->derived_cols.as<T>();
-      a.dld = dld;
-      a.n_rows = n_eval;
-      a.nf = nfk;
-      SrParamArgs<T> pa_{};
-      if (parametric) {  // (the chunk's rows of the table: the kernel indexes it by the chunk-local tree index)
-        pa_.ptab = ctx->ptab.as<T>() + size_t(t0) * size_t(p_stride);
-        pa_.p_stride = int(p_stride);
-        pa_.n_classes = int(pb->n_classes);
-      }
-      a.tiles_per_block = g.tiles;
-      a.n_row_blocks = g.n_row_blocks;
-      a.n_groups = g.n_groups;
-      a.stack_depth = vstk ? std::min(depth, SR_VSTK_SLOTS) : depth;  // (the register-stack trees need <= SR_VSTK_SLOTS)
-      // Σ over n_total rows of values below tbig cannot overflow T, even with rounding slack.
-      a.tbig = T(t_max<T>() / (2.0 * double(n_total > 0 ? n_total : 1)));
-      {  // the view's padded rows over every shard: n_total + at most one 2048-row tile of padding per shard
-        const double padded = double(n_total > 0 ? n_total : 1) + 2048.0 * double(shard ? ctx->comm_ranks : 1);
-        a.big_budget = 64.0 * (t_max<T>() / (1.01 * padded));  // (f64: 64 x DBL_MAX alone is +Inf)
-      }
-      a.track_x = !(max_abs_x < double(a.tbig)) ? 1 : 0;
+  // The argument blocks of one launch over launch positions [p0, p0 + np) of the chunk; its partials
+  // occupy [n_rb][np] words from p0 * n_rb (the chunk's region holds n_rb rows for every position).
+  // out_sum / group_cnt (the reduce's routing), segs and fold_cand are the launch's own (launch_region).
+  void fill_region_args(const BatchChunk<T>& ch, int64_t p0, int64_t np, bool vstk, const Grid& g,
+                        SrEvalArgs<T>* out, SrParamArgs<T>* pout) {
+    const int64_t t0 = ch.t0;
+    const int Rc = vstk ? Rv : R;
+    SrEvalArgs<T>& a = *out = SrEvalArgs<T>{};
+    a.code = static_cast<const SrIns<T>*>(ctx->d_code);
+    a.offsets = ctx->d_off + t0;
+    a.ends = ctx->d_end + t0;
+    a.perm = ctx->d_perm + t0 + p0;
+    a.hint = use_hint ? ctx->hint.as<uint32_t>() + t0 + p0 : nullptr;
+    a.hint_epoch = ctx->hint_epoch;
+    a.n_trees = int(np);
+    a.trees_per_block = g.G;
+    a.X = static_cast<const T*>(ds->X);
+    a.y = static_cast<const T*>(ds->y);
+    a.w = static_cast<const T*>(ds->w);
+    a.row_idx = gather ? ctx->row_idx.as<int64_t>() : nullptr;
+    a.ld = ds->ld;
+    a.derived = dmap.empty() ? nullptr : ctx->derived_cols.as<T>();
+    a.dld = dld;
+    a.n_rows = n_eval;
+    a.nf = nfk;
+    SrParamArgs<T>& pa_ = *pout = SrParamArgs<T>{};
+    if (parametric) {  // (the chunk's rows of the table: the kernel indexes it by the chunk-local tree index)
+      pa_.ptab = ctx->ptab.as<T>() + size_t(t0) * size_t(p_stride);
+      pa_.p_stride = int(p_stride);
+      pa_.n_classes = int(pb->n_classes);
+    }
+    a.tiles_per_block = g.tiles;
+    a.n_row_blocks = g.n_row_blocks;
+    a.n_groups = g.n_groups;
+    a.stack_depth = vstk ? std::min(ch.depth, SR_VSTK_SLOTS) : ch.depth;  // (the register-stack trees need <= SR_VSTK_SLOTS)
+    a.tbig = tbig();
+    {  // the view's padded rows over every shard: n_total + at most one 2048-row tile of padding per shard
+      const double padded = double(n_total > 0 ? n_total : 1) + 2048.0 * double(shard ? ctx->comm_ranks : 1);
+      a.big_budget = 64.0 * (t_max<T>() / (1.01 * padded));  // (f64: 64 x DBL_MAX alone is +Inf)
+    }
+    a.track_x = !(max_abs_x < double(a.tbig)) ? 1 : 0;
 #ifdef SR_TRACK_LITE
-      if (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC) {
-        // (the deferred-check kernels leave +, - of stack values / features and cos, sin, neg, abs,
-        //  sqrt untracked: such a value is at most L x max(tracked max, max|x|, 1) for a tree of L
-        //  nodes, so with tbig / L as the tracked threshold every value stays below tbig, and a tile
-        //  within budget / L - 64 (max|x| + 1) keeps every array's sum within the original budget;
-        //  max|x| < tbig / L here: larger data took the per-node-check tier above)
-        const double L = double(std::max<uint32_t>(1u, max_nodes));
-        a.tbig = T(double(a.tbig) / L);
-        a.big_budget = a.big_budget / L - 64.0 * (max_abs_x + 1.0);
-        a.track_x = 0;
-      }
+    if (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC) {
+      // (the deferred-check kernels leave +, - of stack values / features and cos, sin, neg, abs,
+      //  sqrt untracked: such a value is at most L x max(tracked max, max|x|, 1) for a tree of L
+      //  nodes, so with tbig / L as the tracked threshold every value stays below tbig, and a tile
+      //  within budget / L - 64 (max|x| + 1) keeps every array's sum within the original budget;
+      //  max|x| < tbig / L here: larger data took the per-node-check tier in choose_kernels)
+      const double L = double(std::max<uint32_t>(1u, ch.max_nodes));
+      a.tbig = T(double(a.tbig) / L);
+      a.big_budget = a.big_budget / L - 64.0 * (max_abs_x + 1.0);
+      a.track_x = 0;
+    }
 #endif
-      a.loss_kind = lkind;
-      a.loss_param = T(lparam);
-      a.part_sum = (host_red ? ctx->h_part.as<double>() : ctx->part_sum.as<double>()) + size_t(n_rb) * size_t(t0 + p0);
-      a.part_flag = (host_red ? reinterpret_cast<uint32_t*>(ctx->h_part.as<double>() + n_part)
+    a.loss_kind = lkind;
+    a.loss_param = T(lparam);
+    a.part_sum = (host_red ? ctx->h_part.as<double>() : ctx->part_sum.as<double>()) + size_t(n_rb) * size_t(t0 + p0);
+    a.part_flag = (host_red ? reinterpret_cast<uint32_t*>(ctx->h_part.as<double>() + n_part)
                               : ctx->part_flag.as<uint32_t>()) + size_t(n_rb) * size_t(t0 + p0);
-      a.pred = ctx->pred.as<T>();
-      a.pred_ld = n_eval;
-      if (fold_path == 1) {  // (small calls under the in-order fold: every live tree's losses, [position][rows])
-        a.fold_pos_stride = int64_t(g.n_row_blocks) * int64_t(g.tiles) * 64 * Rc;
-        a.fold_loss = ctx->fold_store.as<T>() + fold_store_at;
-        fold_store_at += size_t(np) * size_t(a.fold_pos_stride);
+    a.pred = ctx->pred.as<T>();
+    a.pred_ld = n_eval;
+    if (fold.path == 1) {  // (small calls under the in-order fold: every live tree's losses, [position][rows])
+      a.fold_pos_stride = int64_t(g.n_row_blocks) * int64_t(g.tiles) * 64 * Rc;
+      a.fold_loss = ctx->fold_store.as<T>() + fold_store_at;
+      fold_store_at += size_t(np) * size_t(a.fold_pos_stride);
+    }
+    // LDS program cache (register-stack launches: 4 workgroups per CU leave ~36 KiB of dynamic LDS
+    // each): sized for the longest group span of this launch, capped by that budget (groups longer
+    // than the cap stream their windows from global memory)
+    a.code_lds = 0;
+    // (round 4's cache in the classic launches too — code_cache 2 — was measured without payoff and
+    //  removed in round 6)
+    const size_t code_budget = vstk ? kCodeCacheLds : 0;
+    if (mode == SR_MODE_LOSS && ctx->code_cache && size_t(g.lds) < code_budget) {
+      const int64_t maxspan = sr_max_group_span(h_perm + t0, h_off + t0, h_end + t0, p0, np, g.G, g.n_groups);
+      const int64_t cap = int64_t((code_budget - size_t(g.lds)) / 16);
+      a.code_lds = int(std::min(maxspan, cap));
+      if (a.code_lds < 64) a.code_lds = 0;
+    }
+  }
+
+  // The dead-tree probe of a launch, from the launch's own arguments.
+  // Trees that are non-finite on the first rows are flagged before the main launch, so its
+  // workgroups skip them from their first tile (without the probe, the ~16 row blocks that
+  // start together evaluate every such tree in full before a hint exists).  Only hints come
+  // out of it: a tree non-finite on some rows of the view is incomplete on the whole view.
+  // a wide, short grid: 16 trees x 1 tile per workgroup, kProbeTiles row blocks; always the
+  // classic kernel at R rows per lane (a register-stack launch's 2x longer tiles would double the
+  // probe's work for the same verdicts: C2's dead trees 0.88 -> 0.6x ms)
+  int launch_probe(const BatchChunk<T>& ch, const SrEvalArgs<T>& a, const SrParamArgs<T>& pa_,
+                   int64_t np, const Grid& g) {
+    SrEvalArgs<T> pa = a;
+    pa.fold_loss = nullptr;  // (its rows are the stress rows; the main launch stores the view's)
+    pa.stack_depth = ch.depth;
+    pa.out_sum = nullptr;
+    pa.out_flag = nullptr;
+    pa.code_lds = 0;  // (its groups differ from the main launch's)
+    pa.group_cnt = nullptr;
+    pa.stamps = nullptr;
+    pa.trees_per_block = std::max(16, g.W);
+    pa.n_groups = int((np + pa.trees_per_block - 1) / pa.trees_per_block);
+    pa.tiles_per_block = 1;
+    pa.n_row_blocks = kProbeTiles;
+    pa.n_rows = std::min<int64_t>(n_eval, int64_t(kProbeTiles) * 64 * R);
+    pa.part_sum = ctx->probe_sum.as<double>();
+    pa.part_flag = ctx->probe_flag.as<uint32_t>();
+    if (stress_probe) {  // the stress rows first (sr_dataset::probe_rows), through the gather build
+      pa.row_idx = static_cast<const int64_t*>(ds->probe_rows);
+      pa.n_rows = std::min<int64_t>(ds->n_probe, int64_t(kProbeTiles) * 64 * R);
+      if (!dmap.empty()) {
+        pa.derived = ctx->probe_derived.as<T>();
+        pa.dld = kProbeRows;
       }
-      // LDS program cache (register-stack launches: 4 workgroups per CU leave ~36 KiB of dynamic LDS
-      // each): sized for the longest group span of this launch, capped by that budget (groups longer
-      // than the cap stream their windows from global memory)
-      a.code_lds = 0;
-      // (round 4's cache in the classic launches too — code_cache 2 — was measured without payoff and
-      //  removed in round 6)
-      const size_t code_budget = vstk ? kCodeCacheLds : 0;
-      if (mode == SR_MODE_LOSS && ctx->code_cache && size_t(g.lds) < code_budget) {
-        int64_t maxspan = 0;
-        for (int64_t q = 0; q < g.n_groups; ++q) {
-          const int64_t pf = p0 + q * g.G, pl = std::min<int64_t>(p0 + np, pf + g.G) - 1;
-          const int64_t sp = int64_t(h_end[t0 + h_perm[t0 + pl]]) - int64_t(h_off[t0 + h_perm[t0 + pf]]);
-          maxspan = std::max(maxspan, sp);
-        }
-        const int64_t cap = int64_t((code_budget - size_t(g.lds)) / 16);
-        a.code_lds = int(std::min(maxspan, cap));
-        if (a.code_lds < 64) a.code_lds = 0;
-      }
-      int64_t n_blocks = g.n_blocks;
-      if (multi) {  // (one launch over the whole chunk: the segments computed above)
-        a.segs = reinterpret_cast<const SrSegment*>(dprog + o_seg);
-        a.n_segs = n_seg;
-        n_blocks = seg_blocks;
-        if (n_blocks > 0x7fffffff) return set_error(SR_ERR_INVALID_ARG, "grid too large");
-      }
-      const bool direct = mode == SR_MODE_LOSS && g.n_row_blocks == 1;
-      if (direct) {  // the interpreter writes the final per-tree values; no reduce launch
-        a.out_sum = ctx->d_out_sum + t0;
-        a.out_flag = ctx->d_out_flag + t0;
-        a.static_bad = ctx->d_bad + t0;
-      }
-      // several row blocks: the last workgroup of each tree group reduces it (no reduce launch)
-      const bool fused = !direct && !host_red && mode == SR_MODE_LOSS && ctx->fused_reduce > 0 &&
-                         int64_t(g.G) * int64_t(g.n_row_blocks) <= ctx->fused_reduce;
-      if (fused) {
-        a.group_cnt = ctx->group_cnt.as<uint32_t>() + t0 + p0;
-        a.fused_sum = ctx->d_out_sum + t0;
-        a.fused_flag = ctx->d_out_flag + t0;
-        a.static_bad = ctx->d_bad + t0;
-      }
-      // mode 2 (default): every chunk after the first (its probe overlaps the first chunk's kernel),
-      // and a single-chunk call when it is large (>= 512 trees x 2^18 rows: the tree-sharding share,
-      // 1,250 trees x 1M rows, 1.09 -> 1.01 ms; the search's small calls pay the probe's launch and
-      // keep none: profiles/r05_ab_probe.txt)
-      // (round 5, later: also the first of two chunks when it is that large — C4's 8M-row shard
-      //  216.9 -> 214.4 ms per call, C2 unchanged; tools/c4_shard_probe.py, profiles/r05_ab_c4_shard.txt)
-      const bool probe_first = nc >= 512 && n_eval >= (int64_t(1) << 18);
-      if (use_probe && p0 == 0 && g.n_row_blocks >= 16 && (ctx->probe != 2 || c > 0 || probe_first)) {
-        // Trees that are non-finite on the first rows are flagged before the main launch, so its
-        // workgroups skip them from their first tile (without the probe, the ~16 row blocks that
-        // start together evaluate every such tree in full before a hint exists).  Only hints come
-        // out of it: a tree non-finite on some rows of the view is incomplete on the whole view.
-        // a wide, short grid: 16 trees x 1 tile per workgroup, kProbeTiles row blocks; always the
-        // classic kernel at R rows per lane (a register-stack launch's 2x longer tiles would double the
-        // probe's work for the same verdicts: C2's dead trees 0.88 -> 0.6x ms)
-        SrEvalArgs<T> pa = a;
-        pa.fold_loss = nullptr;  // (its rows are the stress rows; the main launch stores the view's)
-        pa.stack_depth = depth;
-        pa.out_sum = nullptr;
-        pa.out_flag = nullptr;
-        pa.code_lds = 0;  // (its groups differ from the main launch's)
-        pa.group_cnt = nullptr;
-        pa.stamps = nullptr;
-        pa.trees_per_block = std::max(16, g.W);
-        pa.n_groups = int((np + pa.trees_per_block - 1) / pa.trees_per_block);
-        pa.tiles_per_block = 1;
-        pa.n_row_blocks = kProbeTiles;
-        pa.n_rows = std::min<int64_t>(n_eval, int64_t(kProbeTiles) * 64 * R);
-        pa.part_sum = ctx->probe_sum.as<double>();
-        pa.part_flag = ctx->probe_flag.as<uint32_t>();
-        if (stress_probe) {  // the stress rows first (sr_dataset::probe_rows), through the gather build
-          pa.row_idx = static_cast<const int64_t*>(ds->probe_rows);
-          pa.n_rows = std::min<int64_t>(ds->n_probe, int64_t(kProbeTiles) * 64 * R);
-          if (!dmap.empty()) {
-            pa.derived = ctx->probe_derived.as<T>();
-            pa.dld = kProbeRows;
-          }
-        }
-        if (parametric)
-          SR_HIP_CHECK(sr_launch_eval_param<T>(pa, pa_, mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles, cs));
-        else
-          SR_HIP_CHECK(sr_launch_eval<T>(pa, mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles, cs));
-      }
+    }
+    if (parametric)
+      SR_HIP_CHECK(sr_launch_eval_param<T>(pa, pa_, mode, gather || stress_probe, tier, R, W, false,
+                                           pa.n_groups * kProbeTiles, ch.cs));
+    else
+      SR_HIP_CHECK(sr_launch_eval<T>(pa, mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles, ch.cs));
+    return SR_OK;
+  }
+
+  // One launch of the chunk: its probe, the kernel for it, and its partials' reduce — in the launch, by a
+  // reduce launch, by the fold's pair kernel or (host_red) by the host after the call's synchronisation.
+  int launch_region(const BatchChunk<T>& ch, int64_t p0, int64_t np, bool vstk) {
+    const int64_t t0 = ch.t0;
+    hipStream_t cs = ch.cs;
+    const int Rc = vstk ? Rv : R;
+    const Grid& g = vstk ? ch.g_vs : ch.g_ls;
+    if (g.lds > kLdsMax)
+      return set_error(SR_ERR_TOO_DEEP, "the row tile (" + std::to_string(ds->nf) + " features, " +
+                                            std::to_string(ch.depth) + " stack slots) needs " + std::to_string(g.lds) +
+                                            " bytes of LDS; the limit is 160 KiB");
+    if (g.n_blocks > 0x7fffffff || g.n_row_blocks > n_rb) return set_error(SR_ERR_INVALID_ARG, "grid too large");
+    glast = g;
+    SrEvalArgs<T> a;
+    SrParamArgs<T> pa_;
+    fill_region_args(ch, p0, np, vstk, g, &a, &pa_);
+    int64_t n_blocks = g.n_blocks;
+    if (multi) {  // (one launch over the whole chunk: the segments order_and_stage computed)
+      a.segs = reinterpret_cast<const SrSegment*>(dprog + img.o_seg);
+      a.n_segs = ch.n_seg;
+      n_blocks = ch.seg_blocks;
+      if (n_blocks > 0x7fffffff) return set_error(SR_ERR_INVALID_ARG, "grid too large");
+    }
+    const bool direct = mode == SR_MODE_LOSS && g.n_row_blocks == 1;
+    if (direct) {  // the interpreter writes the final per-tree values; no reduce launch
+      a.out_sum = ctx->d_out_sum + t0;
+      a.out_flag = ctx->d_out_flag + t0;
+      a.static_bad = ctx->d_bad + t0;
+    }
+    // several row blocks: the last workgroup of each tree group reduces it (no reduce launch)
+    const bool fused = !direct && !host_red && mode == SR_MODE_LOSS && ctx->fused_reduce > 0 &&
+                       int64_t(g.G) * int64_t(g.n_row_blocks) <= ctx->fused_reduce;
+    if (fused) {
+      a.group_cnt = ctx->group_cnt.as<uint32_t>() + t0 + p0;
+      a.fused_sum = ctx->d_out_sum + t0;
+      a.fused_flag = ctx->d_out_flag + t0;
+      a.static_bad = ctx->d_bad + t0;
+    }
+    // mode 2 (default): every chunk after the first (its probe overlaps the first chunk's kernel),
+    // and a single-chunk call when it is large (>= 512 trees x 2^18 rows: the tree-sharding share,
+    // 1,250 trees x 1M rows, 1.09 -> 1.01 ms; the search's small calls pay the probe's launch and
+    // keep none: profiles/r05_ab_probe.txt)
+    // (round 5, later: also the first of two chunks when it is that large — C4's 8M-row shard
+    //  216.9 -> 214.4 ms per call, C2 unchanged; tools/c4_shard_probe.py, profiles/r05_ab_c4_shard.txt)
+    const bool probe_first = ch.nc >= 512 && n_eval >= (int64_t(1) << 18);
+    if (use_probe && p0 == 0 && g.n_row_blocks >= 16 && (ctx->probe != 2 || ch.c > 0 || probe_first))
+      SR_STAGE(launch_probe(ch, a, pa_, np, g));
 #ifdef SR_STAMPS
-      ctx->n_stamps = g.n_blocks * g.W * SR_NSTAMPS;
-      SR_HIP_CHECK(ctx->stamps.ensure(size_t(ctx->n_stamps) * sizeof(uint64_t)));
-      SR_HIP_CHECK(hipMemsetAsync(ctx->stamps.p, 0, size_t(ctx->n_stamps) * sizeof(uint64_t), cs));
-      a.stamps = ctx->stamps.as<uint64_t>();
+    ctx->n_stamps = g.n_blocks * g.W * SR_NSTAMPS;
+    SR_HIP_CHECK(ctx->stamps.ensure(size_t(ctx->n_stamps) * sizeof(uint64_t)));
+    SR_HIP_CHECK(hipMemsetAsync(ctx->stamps.p, 0, size_t(ctx->n_stamps) * sizeof(uint64_t), cs));
+    a.stamps = ctx->stamps.as<uint64_t>();
 #endif
-      // (the register-stack launch at 16 rows per lane has the candidate build; the LDS-stack launch's few
-      //  deep trees take the whole FOLD pass)
-      const bool cand_launch = fold_cand && vstk && Rc == 16 && g.W == 4 && g.n_row_blocks > 1;
-      if (cand_launch) a.fold_cand = ctx->fold_cand.as<int4>() + size_t(n_rb) * size_t(t0 + p0);
-      if (parametric)
-        SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
-      else if (cand_launch)
-        SR_HIP_CHECK(sr_launch_loss_cand<T>(a, Rc, g.W, int(n_blocks), cs));
-      else
-        SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
-      if (fold_path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g});
-      if (!direct && !fused && host_red)
-        ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
-      else if (!direct && !fused && !fjob.fuse_reduce)
-        SR_HIP_CHECK(sr_launch_reduce(a.part_sum, a.part_flag, int(np), g.n_row_blocks, a.perm,
-                                    ctx->d_bad + t0, ctx->d_out_sum + t0, ctx->d_out_flag + t0, cs));
-      return SR_OK;
-    };
-    int lrc = SR_OK;
-    if (n_vs > 0) lrc = launch(0, n_vs, true);
-    if (lrc == SR_OK && n_vs < nc) lrc = launch(n_vs, nc - n_vs, false);
-    if (lrc != SR_OK) {
-      sync_both();
-      return lrc;
+    // (the register-stack launch at 16 rows per lane has the candidate build; the LDS-stack launch's few
+    //  deep trees take the whole FOLD pass)
+    const bool cand_launch = fold_cand && vstk && Rc == 16 && g.W == 4 && g.n_row_blocks > 1;
+    if (cand_launch) a.fold_cand = ctx->fold_cand.as<int4>() + size_t(n_rb) * size_t(t0 + p0);
+    if (parametric)
+      SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
+    else if (cand_launch)
+      SR_HIP_CHECK(sr_launch_loss_cand<T>(a, Rc, g.W, int(n_blocks), cs));
+    else
+      SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
+    if (fold.path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g});
+    if (!direct && !fused && host_red)
+      ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
+    else if (!direct && !fused && !fjob.fuse_reduce)
+      SR_HIP_CHECK(sr_launch_reduce(a.part_sum, a.part_flag, int(np), g.n_row_blocks, a.perm, ctx->d_bad + t0,
+                                    ctx->d_out_sum + t0, ctx->d_out_flag + t0, cs));
+    return SR_OK;
+  }
+
+  // the in-order fold of this chunk's complete trees (sr_aux.hip): the launches' partials and flags
+  // are final here (reduce / direct write / in-launch reduction ran on this stream)
+  int fold_chunk(const BatchChunk<T>& ch) {
+    hipStream_t cs = ch.cs;
+    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_fc0[ch.c], cs));
+    SrFoldWho who{ctx->d_out_sum, ctx->d_out_flag, fold_n_terms, nullptr, nullptr, 1};
+    if (fold_mirror) {
+      who.msum = ctx->h_outs.as<double>();
+      who.mflag = reinterpret_cast<uint32_t*>(ctx->h_outs.as<char>() + ctx->outs_flag_off);
     }
-    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_c1[c], cs));
-    if (fold_path && !shard && !fjob.regions.empty()) {
-      // the in-order fold of this chunk's complete trees (sr_aux.hip): the launches' partials and flags
-      // are final here (reduce / direct write / in-launch reduction ran on this stream)
-      if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_fc0[c], cs));
-      SrFoldWho who{ctx->d_out_sum, ctx->d_out_flag, fold_n_terms, nullptr, nullptr, 1};
-      if (fold_mirror) {
-        who.msum = ctx->h_outs.as<double>();
-        who.mflag = reinterpret_cast<uint32_t*>(ctx->h_outs.as<char>() + ctx->outs_flag_off);
-      }
-      for (const FoldRegion<T>& fr : fjob.regions) {
-        int frc = fold_steps<T>(ctx, fjob, fr, who, cs);
-        if (frc == SR_OK) frc = fold_walk<T>(ctx, fjob, fr, who, nullptr, d_fval, d_fst, cs);
-        if (frc != SR_OK) {
-          sync_both();
-          return frc;
-        }
-      }
-      fjob.regions.clear();
-      if (ctx->timed_last) {
-        SR_HIP_CHECK(hipEventRecord(ctx->ev_fc1[c], cs));
-        ctx->fold_timed_last = true;
-      }
+    for (const FoldRegion<T>& fr : fjob.regions) {
+      SR_STAGE(fold_steps<T>(ctx, fjob, fr, who, cs));
+      SR_STAGE(fold_walk<T>(ctx, fjob, fr, who, nullptr, d_fval, d_fst, cs));
     }
+    fjob.regions.clear();
+    if (ctx->timed_last) {
+      SR_HIP_CHECK(hipEventRecord(ctx->ev_fc1[ch.c], cs));
+      ctx->fold_timed_last = true;
+    }
+    return SR_OK;
+  }
+
+  // Chunk c of the call: compile, order and stage, upload, launch each region, fold.
+  int run_chunk(int c) {
+    BatchChunk<T> ch;
+    ch.c = c;
+    SR_STAGE(compile_chunk(ch));
+    SR_STAGE(order_and_stage(ch));
+    SR_STAGE(upload_chunk(ch));
+    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_c0[c], ch.cs));  // the chunk's kernel time includes its probe
+    if (ch.n_vs > 0) SR_STAGE(launch_region(ch, 0, ch.n_vs, true));
+    if (ch.n_vs < ch.nc) SR_STAGE(launch_region(ch, ch.n_vs, ch.nc - ch.n_vs, false));
+    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_c1[c], ch.cs));
+    if (fold.path && !shard && !fjob.regions.empty()) SR_STAGE(fold_chunk(ch));
     ctx->n_chunks_last = c + 1;
-    code_base += uint32_t(ncode);
+    code_base += uint32_t(ch.ncode);
+    return SR_OK;
   }
-  if (n_chunks > 1) {  // the caller continues on the first stream: join the second
-    SR_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->stream2));
-    SR_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0));
+
+  // The stages of a call, in order.
+  int run(Grid* grid_out) {
+    SR_STAGE(validate_call());
+    SR_STAGE(stage_param_table());
+    choose_kernels();
+    SR_STAGE(bind_buffers());
+    in_flight = true;  // (plan_fold's memset is the call's first asynchronous operation)
+    SR_STAGE(plan_fold());
+    SR_STAGE(bind_outputs());
+    SR_STAGE(prepare_hints());
+    SR_STAGE(begin_programs());
+    SR_STAGE(launch_derived());
+    SR_STAGE(begin_chunks());
+    for (int c = 0; c < n_chunks && nt > 0; ++c) SR_STAGE(run_chunk(c));
+    if (n_chunks > 1) {  // the caller continues on the first stream: join the second
+      SR_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->stream2));
+      SR_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0));
+    }
+    if (nt == 0) ctx->mark_phase(0);
+    *grid_out = glast;
+    if (fold.path && shard) ctx->fold_job = std::make_shared<FoldJob<T>>(std::move(fjob));  // (eval_sharded_impl)
+    ctx->mark_phase(1);
+    return SR_OK;
   }
-  if (nt == 0) ctx->mark_phase(0);
-  *grid_out = glast;
-  if (fold_path && shard) ctx->fold_job = std::make_shared<FoldJob<T>>(std::move(fjob));  // (eval_sharded_impl)
-  ctx->mark_phase(1);
-  return SR_OK;
+};
+
+template <typename T>
+int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, const int64_t* row_idx,
+              int64_t n_idx, int64_t n_total, int loss_kind, int mode, SrProgramBatch<T>* prog, Grid* grid_out,
+              bool allow_derived = false, const ShardCtl* shard = nullptr, const ViewSpec* views = nullptr) {
+  BatchCall<T> b{ctx, ds, opset_id, trees, row_idx, n_idx, n_total, loss_kind, mode, prog, allow_derived, shard, views};
+  const int rc = b.run(grid_out);
+  // error exits while work is in flight: no DMA may still read the staging buffers
+  if (rc != SR_OK && b.in_flight) {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+  }
+  return rc;
+}
+// run_batch for the dataset's element type, for the callers that need only ctx->d_out_sum / d_out_flag
+inline int run_batch_any(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, int64_t n_total,
+                         int loss_kind, Grid* grid_out) {
+  if (ds->dtype == SR_DTYPE_F32) {
+    SrProgramBatch<float> prog;
+    return run_batch<float>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, grid_out);
+  }
+  SrProgramBatch<double> prog;
+  return run_batch<double>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, grid_out);
 }
 
 // Interpreter time of the last run_batch (ms): Σ of its launches' durations (as a kernel trace sums
@@ -4071,13 +4063,7 @@ int sr_eval_loss_partials(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const
   SR_HIP_CHECK(hipSetDevice(ctx->device));
   Grid g;
   auto t0 = std::chrono::steady_clock::now();
-  if (ds->dtype == SR_DTYPE_F32) {
-    SrProgramBatch<float> prog;
-    rc = run_batch<float>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, &g);
-  } else {
-    SrProgramBatch<double> prog;
-    rc = run_batch<double>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, &g);
-  }
+  rc = run_batch_any(ctx, ds, opset_id, trees, n_total, loss_kind, &g);
   if (rc != SR_OK || nt == 0) return rc;
   hipStream_t s = ctx->stream;
   const hipMemcpyKind kind = out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -4100,13 +4086,7 @@ int sr_eval_loss_partials_packed(sr_ctx* ctx, const sr_dataset* ds, int opset_id
   SR_HIP_CHECK(hipSetDevice(ctx->device));
   Grid g;
   auto t0 = std::chrono::steady_clock::now();
-  if (ds->dtype == SR_DTYPE_F32) {
-    SrProgramBatch<float> prog;
-    rc = run_batch<float>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, &g);
-  } else {
-    SrProgramBatch<double> prog;
-    rc = run_batch<double>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, &g);
-  }
+  rc = run_batch_any(ctx, ds, opset_id, trees, n_total, loss_kind, &g);
   if (rc != SR_OK || nt == 0) return rc;
   hipStream_t s = ctx->stream;
   const size_t bytes = size_t(5) * size_t(nt) * sizeof(double);
@@ -4213,13 +4193,7 @@ int sr_eval_loss_partials_allreduce(sr_ctx* ctx, const sr_dataset* ds, int opset
   if (rc != SR_OK) return rc;
   Grid g;
   auto t0 = std::chrono::steady_clock::now();
-  if (ds->dtype == SR_DTYPE_F32) {
-    SrProgramBatch<float> prog;
-    rc = run_batch<float>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, &g);
-  } else {
-    SrProgramBatch<double> prog;
-    rc = run_batch<double>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, &g);
-  }
+  rc = run_batch_any(ctx, ds, opset_id, trees, n_total, loss_kind, &g);
   int local = rc;
   hipStream_t s = ctx->stream;
   double* dst = ctx->coll_packed.as<double>();

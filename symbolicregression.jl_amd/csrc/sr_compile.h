@@ -40,15 +40,15 @@ struct SrProgramBatch {
   std::vector<uint32_t> cost;       // estimated device cost per tree (launch ordering / balancing)
   std::vector<uint8_t> depth;       // operand-stack slots each tree needs
   int max_depth = 0;                // operand-stack slots needed (below top-of-stack)
-  int tier = 1;                     // operator tier the programs ran under (SR_TIER_*; set by run_batch):
+  int tier = 1;                     // operator tier the programs ran under (SR_TIER_*; run_batch's begin_programs):
                                     // the exact-sum pass runs the same tier's kernel
   int max_checks = 0;
   int64_t total_nodes = 0;          // Σ count_nodes (metric unit)
   int64_t total_ops = 0;            // Σ operator nodes
   // Lazy form (the caller sets keep_pieces before compiling): `code` stays empty and tree k's
   // offsets[k + 1] - offsets[k] instructions sit at pieces[piece[k]][begin[k]...] (the compile
-  // workers' own buffers), so a caller that re-stages the programs anyway (run_batch, in launch
-  // order) copies them once instead of twice.  n_code counts the instructions in either form.
+  // workers' own buffers), so a caller that re-stages the programs anyway (run_batch's order_and_stage,
+  // in launch order) copies them once instead of twice.  n_code counts the instructions in either form.
   bool keep_pieces = false;
   std::vector<std::vector<SrIns<T>>> pieces;
   std::vector<uint32_t> piece, begin;

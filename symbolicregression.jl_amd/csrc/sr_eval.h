@@ -3,36 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sr_ops.h"
+#include "sr_plan.h"  // modes, tiers, SrSegment, SrDerivedSpec, the launch-shape functions (HIP-free)
 #include "../../include/sr_amd.h"
 
-// SR_MODE_FOLD (round 6): the loss programs of complete trees again, composing each row tile's steps of
-// the reference's in-order loss fold for the binades of the call's fold plan (sr_fold_dev.h), no checks
-enum { SR_MODE_LOSS = 0, SR_MODE_PRED = 1, SR_MODE_EXACT = 2, SR_MODE_FOLD = 3 };
-// operand-stack slots the register-stack kernels hold in VGPRs (1: trees needing a second slot —
-// 6 % of C2's — run on the LDS-stack kernel instead)
 // The deferred checks leave bounded outputs untracked (sr_tile_impl.h sr_untracked_u / _b; round 5:
 // C2 kernel -4 %, arithmetic-only -9 %, profiles/r05_ab_track_lite.txt); -DSR_TRACK_FULL tracks all.
 #ifndef SR_TRACK_FULL
 #define SR_TRACK_LITE 1
 #endif
-#ifndef SR_VSTK_SLOTS
-#define SR_VSTK_SLOTS 2
-#endif
-enum { SR_TIER_BASIC = 0, SR_TIER_FULL = 1 };
-// a flag on the tile kernel's tier template argument: the build for parametric calls (sr_tile_impl.h)
-enum { SR_TIER_PARAM = 2 };
-// another flag there: the loss build that also composes each row block's in-order fold steps under
-// candidate binades (SrEvalArgs::fold_cand; Float32, BASIC, register stack, 16 rows per lane only)
-enum { SR_TIER_CAND = 4 };
-
-// One row view's launch positions in a several-view launch (sr_eval_loss_batch_views): positions
-// [pos0, pos0 + n_pos) in tree groups of trees_per_block, blocks [block0, block0 + groups x row blocks),
-// rows row_idx[row_off .. row_off + n_rows).
-struct SrSegment {
-  int block0, pos0, n_pos, groups;
-  int64_t row_off;
-};
-
 // Per-tree reduction of [row block][position] partials, one wave per tree: lane l folds row blocks
 // l, l + 64, ... in order, then a fixed shfl_xor butterfly adds the 64 lane sums; lane 0 writes the
 // tree's Σ and OR of flags (static_bad ORed in) at perm[position].  The SAME arithmetic serves the
@@ -200,16 +178,6 @@ template <typename T, int R, int MODE, bool GATHER, int TIER, int W = 4, int LK 
 hipError_t sr_launch_tile(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s);
 template <typename T, int R, int MODE, bool GATHER, int TIER, int W = 4, int LK = -1, bool VSTK = false>
 hipError_t sr_launch_tile_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int n_blocks, hipStream_t s);
-// LDS bytes one workgroup (W waves) of the tile kernel needs.
-size_t sr_tile_lds_bytes(int elem_size, int nf, int rows_per_lane, int stack_depth, int trees_per_block,
-                         int max_checks, int waves, bool weighted, int code_lds = 0);
-// Waves per workgroup the dispatcher uses for (mode, tier, rows per lane); `requested` overrides.
-int sr_waves_per_block(int elem_size, int mode, int tier, int rows_per_lane, int requested);
-// Rows per lane the dispatcher uses for (mode, tier); `requested` 4 selects the f32 BASIC tuning kernel.
-template <typename T>
-int sr_rows_per_lane(int mode, int tier, int requested);
-// Rows per lane of the register-stack f32 BASIC loss kernel for n rows (0: use the LDS-stack kernel).
-int sr_vstk_rows(int elem_size, int64_t n_rows, int requested);
 // Runtime dispatch over the instantiated kernels: R rows per lane (sr_rows_per_lane, or
 // sr_vstk_rows with vstk = true: operand stack in VGPRs, programs of <= 2 stack slots).
 template <typename T>
@@ -224,17 +192,10 @@ hipError_t sr_launch_loss_cand(const SrEvalArgs<T>& a, int R, int waves, int n_b
 // smaller set: Float32 BASIC loss at 8 rows per lane (classic, full view or gathered) and 16 (register
 // stack), Float64 at 4 and 8, the FULL tier at 4 / 2, PRED, EXACT with 4 waves (FULL-tier build) and the
 // Float32 FOLD builds of those loss launches; hipErrorInvalidValue for any other shape (the host maps a
-// parametric call's knobs onto this set: sr_capi.cpp run_batch).
+// parametric call's knobs onto this set: sr_capi.cpp choose_kernels).
 template <typename T>
 hipError_t sr_launch_eval_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int mode, bool gather, int tier, int R,
                                 int waves, bool vstk, int n_blocks, hipStream_t s);
-// Derived columns of a call (LOAD_DERIVED): column k = op[k](X[feat[k]]) over the view's rows.
-constexpr int SR_MAX_DERIVED = 32;
-struct SrDerivedSpec {
-  int n;
-  uint8_t op[SR_MAX_DERIVED];
-  uint16_t feat[SR_MAX_DERIVED];  // 0-based feature
-};
 template <typename T>
 hipError_t sr_launch_derived(const T* X, int64_t ld, const int64_t* row_idx, int64_t n_view, int64_t n_pad,
                              const SrDerivedSpec& spec, T* out, int64_t dld, hipStream_t s);

@@ -554,7 +554,8 @@ __device__ __forceinline__ void sr_post_unary(uint32_t u, bool inf, T (&tos)[R])
 // their input (neg, abs, sqrt: max(1, |x|)), or by the sum of their operands' magnitudes (+ and - of two
 // stack values / features); the launch's tbig and BIG budget are divided by the largest tree's node
 // count L, which bounds every untracked value by L x max(tracked max, max|x|, 1) (sr_capi.cpp
-// run_batch).  Data at or above tbig / L runs the per-node-check (FULL tier) kernels instead.
+// fill_region_args).  Data at or above tbig / L runs the per-node-check (FULL tier) kernels instead
+// (choose_kernels).
 #ifdef SR_TRACK_LITE
 constexpr bool sr_untracked_u(uint32_t id) {
   return id == SR_U_COS || id == SR_U_SIN || id == SR_U_NEG || id == SR_U_ABS || id == SR_U_SQRT;
