@@ -521,7 +521,12 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * differ), "fold_store_mb" / "fold_slot_mb" (the fold's stored-loss and slow-segment budgets),
  * "fold_single_pass" (1, the default: a path-2 call's loss launch composes each row block's fold steps
  * under candidate binades, and the FOLD pass runs only the blocks they do not cover; 0: the FOLD
- * pass runs every block of every complete tree), "fold_delta_log2" (the fold plan's window), "fold_seg_max" (the longest row block folded: a folding
+ * pass runs every block of every complete tree), "fold_cand_est" (1, the default: those candidates are
+ * chosen from the tree's running prefix — the row blocks other workgroups have already finished — once
+ * "fold_cand_est_min" of them have, 4 by default; 0: from the block's first tile alone; `taken` and `rerun`
+ * of sr_last_fold_cand then vary from run to run, their sum and every result do not), "fold_compact" (1, the
+ * default: the FOLD pass of a plain path-2 call runs over per-row-block lists of the positions left to it;
+ * 0: over the loss launch's grid), "fold_delta_log2" (the fold plan's window), "fold_seg_max" (the longest row block folded: a folding
  * call takes enough row blocks for it), "fold_rows_max" (the longest fold, 2^24 rows: a longer call —
  * C4's 2^26 rows — keeps the f64 sum, as "ref_fold" 0).  Results do not depend on any knob but these
  * three ("ref_fold", "fold_seg_max", "fold_rows_max": whether a call folds) and — without the fold only

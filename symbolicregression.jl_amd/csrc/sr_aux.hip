@@ -718,6 +718,76 @@ __global__ void __launch_bounds__(256) sr_fold_plan_kernel(const double* __restr
   }
 }
 
+// The compacted FOLD launch's work lists (SrEvalArgs::fold_list): the FOLD pass runs few of a row block's
+// positions once the plan has taken the rest from the loss launch's candidates, so a launch over the loss
+// launch's grid would stage tiles for workgroups with one or two trees per wave.  One workgroup per row
+// block keeps, in launch order (stable: the loss launch's cost ordering still balances the waves), the
+// positions the FOLD pass runs — exactly its own rule: a code other than SKIP and a pair not TAKEN.
+__global__ void __launch_bounds__(256) sr_fold_compact_kernel(const int32_t* __restrict__ code,
+                                                              const int32_t* __restrict__ sq, int np,
+                                                              int32_t* __restrict__ list, int32_t* __restrict__ cnt) {
+  __shared__ int s_w[4];
+  const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  const size_t row = size_t(blockIdx.x) * size_t(np);
+  int base = 0;  // (uniform: the entries kept so far)
+  for (int p0 = 0; p0 < np; p0 += 256) {
+    const int p = p0 + tid;
+    const bool keep = p < np && code[row + size_t(p)] != SR_FCODE_SKIP && sq[row + size_t(p)] != SR_FSQ_TAKEN;
+    const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
+    if (lane == 0) s_w[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_w[w];
+      before += w < wave ? c : 0;
+      total += c;
+    }
+    if (keep) list[row + size_t(base + before + __popcll(m & ((uint64_t(1) << lane) - 1u)))] = p;
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) cnt[blockIdx.x] = base;
+}
+// ... and each row block's first workgroup, G entries per workgroup: wg0[rb] = the exclusive scan of
+// ceil(cnt / G), wg0[n_rb] the launch's live workgroups (one workgroup).
+__global__ void __launch_bounds__(256) sr_fold_compact_scan_kernel(const int32_t* __restrict__ cnt, int n_rb, int G,
+                                                                   int32_t* __restrict__ wg0) {
+  __shared__ int s_w[4];
+  const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  int base = 0;
+  for (int r0 = 0; r0 < n_rb; r0 += 256) {
+    const int r = r0 + tid;
+    const int v = r < n_rb ? (cnt[r] + G - 1) / G : 0;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(inc, off, 64);
+      if (lane >= off) inc += o;
+    }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_w[w];
+      before += w < wave ? c : 0;
+      total += c;
+    }
+    if (r < n_rb) wg0[r] = base + before + inc - v;
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) wg0[n_rb] = base;
+}
+hipError_t sr_launch_fold_compact(const SrFoldTabs& ft, int np, int n_rb, int G, int32_t* list, int32_t* cnt,
+                                  int32_t* wg0, hipStream_t s) {
+  if (np <= 0 || n_rb <= 0 || G <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sr_fold_compact_kernel, dim3(unsigned(n_rb)), dim3(256), 0, s, ft.code, ft.sq, np, list, cnt);
+  hipLaunchKernelGGL(sr_fold_compact_scan_kernel, dim3(1), dim3(256), 0, s, cnt, n_rb, G, wg0);
+  return hipGetLastError();
+}
+
 // The fold's first rows one by one (Statistics.mean / Base.sum over a generator: the first loss starts
 // the fold), in the hardware's own adds — the running value leaves a binade every few rows here, so a
 // round per crossing would cost ~1 us each.  Rows [0, ks), ks <= 256, of a stored segment b; one wave

@@ -324,6 +324,18 @@ struct sr_ctx {
   // two passes.
   int fold_single_pass = 1;
   DevBuf fold_cand;          // the candidates, [row block][position] int4 (sr_fold_dev.h)
+  // SR_AMD_FOLD_COMPACT / "fold_compact": the FOLD pass of a plain path-2 call runs over per-row-block lists
+  // of the positions the plan left it (sr_fold_compact_kernel), G per workgroup, instead of the loss
+  // launch's (row block, tree group) grid (0).  Gathered, parametric and row-sharded calls keep the grid.
+  int fold_compact = 1;
+  DevBuf fold_list;          // [row block][position] int32, laid out as the partials
+  DevBuf fold_wg;            // per region (2 per chunk): {cnt [n_rb], wg0 [n_rb + 1]}
+  // SR_AMD_FOLD_CAND_EST / "fold_cand_est": the candidates' guess from the tree's running prefix (the row
+  // blocks other workgroups have finished; 0: the block's first tile only); usable from fold_cand_est_min
+  // finished blocks on (SR_AMD_FOLD_CAND_EST_MIN; tools/fold_cand_sim.py)
+  int fold_cand_est = 1;
+  int fold_cand_est_min = 4;
+  DevBuf fold_est;           // per launch position: {f64 sum [nt] | u32 count [nt]}, zeroed by every call
   bool fold_cand_read = true;  // fold_ctl's counters of the last call are in n_cand_* below
   int64_t n_cand_taken_last = 0, n_cand_rerun_last = 0;
   int fold_walk_dbg = 0;     // SR_AMD_FOLD_WALK_DBG (analysis): 2 no O(1) slow blocks, 4 no serial start
@@ -472,6 +484,7 @@ struct FoldRegion {
   int Rc;
   bool vstk;
   Grid g;
+  int idx = -1;  // its place among the call's regions (the compacted FOLD launch's counters); -1: no compaction
   int64_t rb_rows() const { return int64_t(g.tiles) * 64 * Rc; }
   // the region's offset in the partial buffers of n_rb row blocks per position, and its plan arrays there
   size_t off(int64_t n_rb) const { return size_t(n_rb) * size_t(pos0); }
@@ -555,6 +568,21 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
   fa.fold_slot_rows = job.slot_rows;
   fa.fold_pos_stride = 0;
   fa.fold_cand = nullptr;
+  fa.fold_est_sum = nullptr;
+  fa.fold_est_cnt = nullptr;
+  // the compacted launch (sr_ctx::fold_compact): plain single-GPU calls over the full view; the grid stays the
+  // region's (an upper bound: the list's workgroups come first, the rest return at once)
+  if (ctx->fold_compact && fr.idx >= 0 && !fr.p.ptab && !job.gather && fr.a.segs == nullptr && who.elig == nullptr &&
+      who.est == nullptr) {
+    int32_t* cnt = ctx->fold_wg.as<int32_t>() + sr_fold_wg_off(fr.idx, job.n_rb);
+    int32_t* wg0 = cnt + job.n_rb;
+    int32_t* list = ctx->fold_list.as<int32_t>() + fr.off(job.n_rb);
+    SR_HIP_CHECK(sr_launch_fold_compact(ft, np, nrb, fr.a.trees_per_block, list, cnt, wg0, cs));
+    fa.fold_list = list;
+    fa.fold_cnt = cnt;
+    fa.fold_wg0 = wg0;
+    fa.code_lds = 0;  // (a listed workgroup's programs are no contiguous span: no LDS program cache)
+  }
   if (fr.p.ptab)  // (a parametric call's launches: the PARAM builds)
     SR_HIP_CHECK(sr_launch_eval_param<T>(fa, fr.p, SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, int(fr.n_blocks), cs));
   else
@@ -661,7 +689,7 @@ struct BatchCall {
   // plan_fold / bind_outputs / prepare_hints
   int64_t fold_n_terms = 0;
   FoldPlan fold;
-  bool fold_cand = false;
+  bool fold_cand = false, fold_compact = false;
   bool host_out = false, fold_mirror = false, host_red = false, use_hint = false, use_probe = false, stress_probe = false;
   // launch_derived: the derived-column spec and map, the columns' leading dimension, the call's leaf bound
   std::vector<int16_t> dmap;
@@ -875,6 +903,16 @@ struct BatchCall {
     fold_cand = fold.path == 2 && ctx->fold_single_pass && sizeof(T) == 4 && tier == SR_TIER_BASIC && !gather &&
                 !multi && !shard && ctx->param == nullptr && n_rb > 1;
     if (fold_cand) SR_HIP_CHECK(ctx->fold_cand.ensure(n_part * sizeof(int4) + 16));
+    if (fold_cand && ctx->fold_cand_est) {  // every position's running prefix {sum | count}: none finished yet
+      SR_HIP_CHECK(ctx->fold_est.ensure(size_t(nt) * (sizeof(double) + sizeof(uint32_t)) + 8));
+      SR_HIP_CHECK(hipMemsetAsync(ctx->fold_est.p, 0, size_t(nt) * (sizeof(double) + sizeof(uint32_t)), s));
+    }
+    // the compacted FOLD launch (sr_ctx::fold_compact): plain calls only
+    fold_compact = fold.path == 2 && ctx->fold_compact && !gather && !multi && !shard && ctx->param == nullptr;
+    if (fold_compact) {
+      SR_HIP_CHECK(ctx->fold_list.ensure(n_part * sizeof(int32_t) + 4));
+      SR_HIP_CHECK(ctx->fold_wg.ensure(sr_fold_wg_words(n_rb) * sizeof(int32_t)));
+    }
     if (!ctx->internal_pass) {  // (the fallback's prediction passes leave the call's record alone)
       ctx->fold_path_last = fold.path;
       ctx->fold_timed_last = false;
@@ -1369,13 +1407,18 @@ struct BatchCall {
     //  deep trees take the whole FOLD pass)
     const bool cand_launch = fold_cand && vstk && Rc == 16 && g.W == 4 && g.n_row_blocks > 1;
     if (cand_launch) a.fold_cand = ctx->fold_cand.as<int4>() + size_t(n_rb) * size_t(t0 + p0);
+    if (cand_launch && ctx->fold_cand_est) {  // (plan_fold zeroed them)
+      a.fold_est_sum = ctx->fold_est.as<double>() + t0 + p0;
+      a.fold_est_cnt = reinterpret_cast<uint32_t*>(ctx->fold_est.as<double>() + nt) + t0 + p0;
+      a.fold_est_min = uint32_t(ctx->fold_cand_est_min);
+    }
     if (parametric)
       SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
     else if (cand_launch)
       SR_HIP_CHECK(sr_launch_loss_cand<T>(a, Rc, g.W, int(n_blocks), cs));
     else
       SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
-    if (fold.path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g});
+    if (fold.path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g, fold_compact ? sr_fold_region(ch.c, vstk) : -1});
     if (!direct && !fused && host_red)
       ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
     else if (!direct && !fused && !fjob.fuse_reduce)
@@ -3745,6 +3788,9 @@ int sr_init(int device, sr_ctx** out) {
   if (const char* v = std::getenv("SR_AMD_FOLD_REDUCE")) ctx->fold_reduce = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_PRE_START")) ctx->fold_pre_start = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_SINGLE_PASS")) ctx->fold_single_pass = std::atoi(v) != 0 ? 1 : 0;
+  if (const char* v = std::getenv("SR_AMD_FOLD_COMPACT")) ctx->fold_compact = std::atoi(v) != 0 ? 1 : 0;
+  if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST")) ctx->fold_cand_est = std::atoi(v) != 0 ? 1 : 0;
+  if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST_MIN")) ctx->fold_cand_est_min = std::max(1, std::atoi(v));
   hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e == hipSuccess && std::getenv("SR_AMD_EAGER_STREAM2")) e = ctx->need_stream2();  // (A/B: the round-4 layout)
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming);
@@ -3791,7 +3837,7 @@ int sr_shutdown(sr_ctx* ctx) {
                       &ctx->hint, &ctx->jsum_prog, &ctx->jsum_scratch, &ctx->probe_sum, &ctx->probe_flag, &ctx->g_code, &ctx->g_offsets, &ctx->g_consts, &ctx->g_const_off,
                       &ctx->g_items, &ctx->g_part, &ctx->g_out, &ctx->derived_cols, &ctx->probe_derived, &ctx->coll_buf, &ctx->coll_packed, &ctx->ctl, &ctx->fold_io, &ctx->group_cnt,
                       &ctx->fold_code, &ctx->fold_tab, &ctx->fold_store, &ctx->fold_ctl, &ctx->fold_io2, &ctx->fold_sq,
-                      &ctx->fold_tab2, &ctx->ptab, &ctx->fold_cand})
+                      &ctx->fold_tab2, &ctx->ptab, &ctx->fold_cand, &ctx->fold_list, &ctx->fold_wg, &ctx->fold_est})
       b->release();
     for (HostBuf* b : {&ctx->h_prog, &ctx->h_outs, &ctx->h_grad, &ctx->h_coll, &ctx->h_part, &ctx->h_exact, &ctx->h_ptab})
       b->release();
@@ -4569,6 +4615,18 @@ int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value) {
   }
   if (std::strcmp(name, "fold_single_pass") == 0) {  // candidate binades in the loss launch (SR_AMD_FOLD_SINGLE_PASS)
     ctx->fold_single_pass = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "fold_compact") == 0) {  // the FOLD pass over per-row-block work lists (SR_AMD_FOLD_COMPACT)
+    ctx->fold_compact = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "fold_cand_est") == 0) {  // the candidates' guess from the running prefix (SR_AMD_FOLD_CAND_EST)
+    ctx->fold_cand_est = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "fold_cand_est_min") == 0) {  // finished row blocks that make it usable (SR_AMD_FOLD_CAND_EST_MIN)
+    ctx->fold_cand_est_min = int(value < 1 ? 1 : (value > (1 << 30) ? (1 << 30) : value));
     return SR_OK;
   }
   if (std::strcmp(name, "fold_debug_fail") == 0) {  // tests: trees t % value == 0 take the fold's fallback

@@ -162,6 +162,20 @@ struct SrEvalArgs {
   // the plan takes a steps block's pair from here when its binade is one of them, and the FOLD pass then
   // skips the block
   int4* fold_cand;
+  // FOLD, the compacted launch (NULL: workgroup = (row block, tree group) as in the loss launch): per row
+  // block rb the launch positions the FOLD pass must run, in launch order, fold_list[rb * n_trees + k],
+  // k < fold_cnt[rb]; workgroups fold_wg0[rb] .. fold_wg0[rb + 1] - 1 take G of them each
+  // (fold_wg0[n_row_blocks]: the total; workgroups past it return at once).  sr_fold_compact_kernel.
+  const int32_t* fold_list;
+  const int32_t* fold_cnt;
+  const int32_t* fold_wg0;
+  // SR_TIER_CAND loss builds, the candidates' guess from the running prefix (NULL: the first-tile guess
+  // only): per position, the f64 sum of the row blocks finished so far and their count (relaxed
+  // agent-scope adds at a workgroup's end; a workgroup reads its trees' pair at its start: only ever a
+  // guess), usable from fold_est_min blocks on.  Zeroed by the host before the call.
+  double* fold_est_sum;
+  uint32_t* fold_est_cnt;
+  uint32_t fold_est_min;
 };
 // A parametric call's table: ptab[tree * p_stride + k * n_classes + class] at the caller's tree index (as
 // `offsets`).  The rows' 0-based classes are the last staged X row (the dataset's hidden row:
@@ -310,6 +324,10 @@ template <typename T>
 hipError_t sr_launch_fold_plan(const double* part, int np, int n_rb, const uint32_t* perm, const SrFoldWho& who,
                                double delta, SrFoldTabs ft, int* slot_next, int slot_cap, const int4* cand,
                                hipStream_t s);
+// The compacted FOLD launch's lists from a region's plan (SrEvalArgs::fold_list / fold_cnt / fold_wg0; G:
+// the launch's trees per workgroup): list [n_rb][np], cnt [n_rb], wg0 [n_rb + 1].
+hipError_t sr_launch_fold_compact(const SrFoldTabs& ft, int np, int n_rb, int G, int32_t* list, int32_t* cnt,
+                                  int32_t* wg0, hipStream_t s);
 template <typename T>
 hipError_t sr_launch_fold_stab(const double* part, int np, int n_rb, int64_t rb_rows, int64_t n, const uint32_t* perm,
                                const SrFoldWho& who, double delta, const T* losses, SrFoldTabs ft,

@@ -34,13 +34,25 @@ constexpr int32_t SR_FSQ_TAKEN = 0x7fffffff;
 // candidate binade q0 (SKIP: none — the first row block, a tree found dead), y / z / w = the block's
 // composed step under q0 / q0 + 1 / q0 + 2 when that candidate was composed and no tile of the block has
 // an exact half-ulp tie under it (the pair is then (t, t), bit for bit the FOLD pass's), else
-// SR_FCAND_TIE.  SR_FCAND_N adjacent binades are composed: the two nearest the guess g of the running
-// sum at the block (its first tile's sum times the tiles before the block), q0 = the binade of g / sqrt 2
-// — g in the lower half of its binade (in log scale) takes that binade and the one below, g in the upper
-// half that binade and the one above.  (Three — q^ - 1, q^, q^ + 1 around g's binade — took 78.7 % of
-// C2's blocks against 78.1 % and cost 40 % more in the loss epilogue: DESIGN §12.)
+// SR_FCAND_TIE.  SR_FCAND_N adjacent binades from q0 up are composed, chosen from a guess g of the running
+// sum at the block: when enough of the tree's row blocks have already finished in other workgroups
+// (SrEvalArgs::fold_est_sum / fold_est_cnt / fold_est_min), g = their mean sum times the blocks before
+// this one — the whole view's scale, which heavy-tailed trees (exp, /) need; otherwise the block's first
+// tile's sum times the tiles before the block (1,024 rows extrapolated over up to a million).
+// One candidate (the default): g's own binade.  Two (-DSR_FCAND_N=2): q0 = the binade of g / sqrt 2 — g in
+// the lower half of its binade (in log scale) takes that binade and the one below, g in the upper half
+// that binade and the one above.  With the first-tile guess alone two were worth their cost (78.1 % of
+// C2's blocks taken against 71.2 %; three — q^ - 1 .. q^ + 1 — took 78.7 % and cost 40 % more in the loss
+// epilogue); with the prefix guess one takes 91.4 % and two 93.7 %, and the second candidate costs more in
+// the loss launch than the FOLD pass saves: DESIGN §12.
 constexpr int32_t SR_FCAND_TIE = -1;
-constexpr int SR_FCAND_N = 2;
+#ifndef SR_FCAND_N
+#define SR_FCAND_N 1
+#endif
+// the lowest candidate is the binade of SR_FCAND_SCALE x the guess
+constexpr double SR_FCAND_SCALE = SR_FCAND_N == 1 ? 1.0 : (SR_FCAND_N == 2 ? 0.7071067811865476 : 0.5);
+// a lane's candidate binade before any guess is made (never a binade, and not SKIP)
+constexpr int32_t SR_FCAND_UNSET = int32_t(0x80000001u);
 // per-tree status of the walk (sr_fold_walk_kernel): not folded / the fold's exact value / the plan's
 // speculated binades missed (the host folds that tree through the prediction pass instead)
 enum { SR_FST_NONE = 0, SR_FST_OK = 1, SR_FST_FAIL = 2 };

@@ -429,3 +429,9 @@ inline FoldPlan sr_fold_plan(const FoldPlanIn& in) {
   }
   return out;
 }
+// The compacted FOLD launch (sr_ctx::fold_compact): a call has at most two launches per chunk (register
+// stack, LDS stack), each with its own counters {cnt [n_rb] | wg0 [n_rb + 1]}; region r's start, in words,
+// for a call of n_rb row blocks per position, and the call's words.
+inline int sr_fold_region(int chunk, bool vstk) { return 2 * chunk + (vstk ? 0 : 1); }
+inline size_t sr_fold_wg_off(int region, int64_t n_rb) { return size_t(region) * (2 * size_t(n_rb) + 2); }
+inline size_t sr_fold_wg_words(int64_t n_rb) { return sr_fold_wg_off(2 * kMaxChunks, n_rb); }

@@ -896,7 +896,22 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   // tree group fastest: the blocks resident at one time share few row blocks (X stays in L2)
   int tg, rb, tree0, gcount;
   const int64_t* ridx = a.row_idx;  // GATHER: this block's row view
-  if (a.segs == nullptr) {
+  // FOLD, the compacted launch: the workgroup's row block and its G entries of that block's list (tree0:
+  // the first one's index in the list, not a launch position)
+  const bool listed = (MODE == SR_MODE_FOLD) && a.fold_list != nullptr;
+  if (listed) {
+    if (int(blockIdx.x) >= a.fold_wg0[a.n_row_blocks]) return;  // (the grid is the loss launch's: an upper bound)
+    int lo = 0, hi = a.n_row_blocks - 1;
+    while (lo < hi) {  // the last row block starting at or before this workgroup (an empty one starts where the next does)
+      const int mid = (lo + hi + 1) >> 1;
+      if (a.fold_wg0[mid] <= int(blockIdx.x)) lo = mid;
+      else hi = mid - 1;
+    }
+    rb = lo;
+    tg = int(blockIdx.x) - a.fold_wg0[rb];
+    tree0 = tg * G;
+    gcount = a.fold_cnt[rb] - tree0;
+  } else if (a.segs == nullptr) {
     tg = int(blockIdx.x) % a.n_groups;
     rb = int(blockIdx.x) / a.n_groups;
     tree0 = tg * G;
@@ -929,7 +944,10 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
 
   // this wave's slots
   const int S = gcount > wave ? (gcount - wave + SR_WAVES - 1) / SR_WAVES : 0;
-  const int my_pos = tree0 + wave + SR_WAVES * lane;
+  int my_pos = tree0 + wave + SR_WAVES * lane;
+  if (MODE == SR_MODE_FOLD) {  // (the compacted launch: the listed launch position)
+    if (listed) my_pos = lane < S ? a.fold_list[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)] : 0;
+  }
   uint32_t my_pb = 0u, my_pe = 0u;
   uint32_t my_t = 0u;  // PARAM: the caller's index of lane j's tree (its rows of the parameter table)
   if (lane < S) {
@@ -954,8 +972,9 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   // LDS program cache (LOSS): the group's programs are one contiguous span of the launch-ordered code
   // (first position's start .. last position's end); copied once, read by every tile's windows
   const uint4* lcode = reinterpret_cast<const uint4*>(sr_smem + plan.code);
+  // (a compacted FOLD workgroup's programs are no span: its windows stream from global memory)
   bool lds_code = false;
-  if ((MODE == SR_MODE_LOSS || MODE == SR_MODE_FOLD) && a.code_lds > 0 && a.ends != nullptr && gcount > 0) {
+  if ((MODE == SR_MODE_LOSS || MODE == SR_MODE_FOLD) && a.code_lds > 0 && a.ends != nullptr && gcount > 0 && !listed) {
     const uint32_t t_first = a.perm ? a.perm[tree0] : uint32_t(tree0);
     const uint32_t t_last = a.perm ? a.perm[tree0 + gcount - 1] : uint32_t(tree0 + gcount - 1);
     const uint32_t gbase = __builtin_amdgcn_readfirstlane(a.offsets[t_first]);
@@ -976,11 +995,26 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   // FOLD: lane j's tree's composed steps over this row block (a slow segment's: under my_sq, and under
   // my_sq + 1 in facc2 / facc3)
   typename SrFoldTab<T>::I facc0 = 0, facc1 = 0, facc2 = 0, facc3 = 0;
-  // CAND: lane j's tree's lowest candidate binade q0 on this row block (from its first tile's sum) and the
-  // block's steps so far under q0, q0 + 1, ... (SR_FCAND_TIE once a tile has a tie under that binade)
-  int32_t cand_q = SR_FCODE_SKIP;
-  int32_t cand[3] = {0, 0, SR_FCAND_TIE};
+  // CAND: lane j's tree's lowest candidate binade q0 on this row block (from the tree's running prefix, else
+  // from the block's first tile's sum) and the block's steps so far under q0, q0 + 1, ... (SR_FCAND_TIE once a
+  // tile has a tie under that binade, and for the candidates the build does not compose)
+  int32_t cand_q = SR_FCAND_UNSET;
+  int32_t cand[3] = {0, SR_FCAND_N > 1 ? 0 : SR_FCAND_TIE, SR_FCAND_N > 2 ? 0 : SR_FCAND_TIE};
   static_assert(SR_FCAND_N >= 1 && SR_FCAND_N <= 3, "the candidates of a block are one int4");
+  // CAND: the guess from the running prefix — the mean of the tree's row blocks finished so far (other
+  // workgroups' relaxed adds at their end, below) times the blocks before this one; only ever a guess.
+  // Taken before the tile loop, so nothing of it stays live through the interpreter.
+  if constexpr (CAND) {
+    if (a.fold_est_sum != nullptr && rb > 0 && lane < S) {
+      const uint32_t n = __hip_atomic_load(a.fold_est_cnt + my_pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (n >= a.fold_est_min) {
+        const double sm = __longlong_as_double(static_cast<long long>(
+            __hip_atomic_load(reinterpret_cast<unsigned long long*>(a.fold_est_sum + my_pos), __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT)));
+        cand_q = sr_fold_q<T>(sm / double(n) * double(rb) * SR_FCAND_SCALE);
+      }
+    }
+  }
   uint64_t dmask = 0u, bmask = 0u, emask = 0u;
   double accv = 0.0;
   // dead-tree hints shared across row blocks (LOSS mode): a tree found non-finite by any block is
@@ -1448,15 +1482,14 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
                 if (rb > 0 && a.fold_cand != nullptr) {
                   using I = typename SrFoldTab<T>::I;
                   constexpr I CAP = I(1) << (SrFoldTraits<T>::mant + 3);
-                  int32_t qh;
-                  if (tile == 0) {
-                    qh = sr_fold_q<T>(double(s) * double(a.tiles_per_block) * double(rb) * 0.7071067811865476);
+                  // (no guess from the running prefix: the first tile's sum times the tiles before the block)
+                  int32_t qh = __builtin_amdgcn_readlane(cand_q, j);
+                  if (tile == 0 && qh == SR_FCAND_UNSET) {
+                    qh = sr_fold_q<T>(double(s) * double(a.tiles_per_block) * double(rb) * SR_FCAND_SCALE);
                     qh = __builtin_amdgcn_readfirstlane(qh);
                     if (lane == j) cand_q = qh;
-                  } else {
-                    qh = __builtin_amdgcn_readlane(cand_q, j);
                   }
-                  if (qh != SR_FCODE_SKIP) {
+                  if (qh != SR_FCAND_UNSET) {
                     I ct[SR_FCAND_N];
                     bool cok[SR_FCAND_N];
                     sr_fold_tile_fast_n<T, R, SR_FCAND_N>(lc, qh, ct, cok);
@@ -1563,7 +1596,13 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   if constexpr (CAND) {
     if (a.fold_cand != nullptr && lane < S)
       a.fold_cand[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)] =
-          make_int4(((dmask >> lane) & 1u) ? SR_FCODE_SKIP : cand_q, cand[0], cand[1], cand[2]);
+          make_int4((((dmask >> lane) & 1u) || cand_q == SR_FCAND_UNSET) ? SR_FCODE_SKIP : cand_q, cand[0], cand[1],
+                    cand[2]);
+    // this block's sum joins the tree's running prefix for the workgroups that start later
+    if (a.fold_est_sum != nullptr && ((live & ~dmask) >> lane) & 1u) {
+      __hip_atomic_fetch_add(a.fold_est_sum + my_pos, accv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(a.fold_est_cnt + my_pos, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
   if (lane < S) {
     uint32_t f = (((dmask >> lane) & 1u) ? SR_FLAG_NONFINITE : 0u) | (((bmask >> lane) & 1u) ? SR_FLAG_BIG : 0u) |

@@ -68,7 +68,10 @@ class DeviceContext:
         "ref_fold" (the in-order loss fold: 1 default, 0 the f64 sums), "fold_seg_max" / "fold_rows_max"
         (the longest row block / fold folded: past them a call keeps the f64 sums — these three are the
         knobs results depend on), "fold_store_mb", "fold_slot_mb", "fold_delta_log2", "fold_single_pass" (the
-        loss launch of a FOLD-mode call composes the fold's steps under candidate binades: 1 default); tests:
+        loss launch of a FOLD-mode call composes the fold's steps under candidate binades: 1 default),
+        "fold_cand_est" / "fold_cand_est_min" (those binades guessed from the tree's running prefix: 1 default,
+        from 4 finished row blocks on), "fold_compact" (the FOLD pass runs over per-row-block work lists: 1
+        default); tests:
         "inject_failure*", "debug_hint_regrow", "fold_debug_fail"."""
         _lib.check(_lib.lib.sr_set_tuning(self.handle, name.encode(), int(value)))
 

@@ -283,6 +283,19 @@ void fold_grids(FoldPlanIn* in) {
 
 void check_fold() {
   const int64_t M = int64_t(1) << 20;
+  {  // the compacted FOLD launch's counters: every region of a call its own {cnt [n_rb] | wg0 [n_rb + 1]}
+    for (int64_t n_rb : {1, 20, 512, 4096}) {
+      size_t end = 0;
+      for (int c = 0; c < kMaxChunks; ++c)
+        for (bool vstk : {true, false}) {
+          const int r = sr_fold_region(c, vstk);
+          CHECK(r >= 0 && r < 2 * kMaxChunks);
+          CHECK(sr_fold_wg_off(r, n_rb) >= end);  // (regions in launch order, none overlapping the last)
+          end = sr_fold_wg_off(r, n_rb) + size_t(n_rb) + size_t(n_rb + 1);
+        }
+      CHECK(end <= sr_fold_wg_words(n_rb));
+    }
+  }
   {  // 100 trees x 1,000 rows: two row blocks of 512, 400 KiB of losses: stored
     FoldPlanIn in = fold_in(4, 100, 1000, 1000, 1000, 8, 0);
     fold_grids(&in);
