@@ -526,7 +526,13 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * "fold_cand_est_min" of them have, 4 by default; 0: from the block's first tile alone; `taken` and `rerun`
  * of sr_last_fold_cand then vary from run to run, their sum and every result do not), "fold_compact" (1, the
  * default: the FOLD pass of a plain path-2 call runs over per-row-block lists of the positions left to it;
- * 0: over the loss launch's grid), "fold_delta_log2" (the fold plan's window), "fold_seg_max" (the longest row block folded: a folding
+ * 0: over the loss launch's grid), "tail_chunk" (4, the default: such a call whose loss launch composes
+ * candidates runs three tree chunks — 1 / "first_chunk", the rest, the last value/12 of the trees (1..6), each
+ * of at least "chunk_min" trees — whose last two fold chains run side by side; 0: the two-chunk pipeline),
+ * "exact_early" (1, the default: a multi-chunk call under the fold copies its flags to pinned memory behind
+ * the last chunk's reduce and runs the exact-sum pass beside the last fold chains; 0: after the call's
+ * device work) — with the two at 0 a call's launch sequence is the two-chunk pipeline's —,
+ * "fold_delta_log2" (the fold plan's window), "fold_seg_max" (the longest row block folded: a folding
  * call takes enough row blocks for it), "fold_rows_max" (the longest fold, 2^24 rows: a longer call —
  * C4's 2^26 rows — keeps the f64 sum, as "ref_fold" 0).  Results do not depend on any knob but these
  * three ("ref_fold", "fold_seg_max", "fold_rows_max": whether a call folds) and — without the fold only

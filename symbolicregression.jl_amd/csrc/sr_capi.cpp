@@ -134,6 +134,25 @@ struct sr_ctx {
   hipError_t need_stream2() {
     return stream2 ? hipSuccess : hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking);
   }
+  // SR_AMD_TAIL_CHUNK / "tail_chunk": a plain path-2 call whose loss launch composes candidates (C2's) runs
+  // three chunks {1 / first_chunk, the rest, tail_chunk / 12} of the trees (sr_chunk_plan): the last two loss
+  // launches end close together and their fold chains — latency-bound, each on its chunk's stream — run
+  // side by side instead of one chain of 5/6 of the trees alone; 0: the two-chunk schedule
+  int tail_chunk = 4;
+  // SR_AMD_EXACT_EARLY / "exact_early": a multi-chunk loss call under the in-order fold copies its flags to
+  // pinned memory behind the last chunk's reduce (every chunk's flags are final there) and records ev_flags;
+  // eval_loss_finish waits for that event alone, lists the BIG trees and enqueues the exact-sum pass on a
+  // third stream, which no chain occupies, so the pass runs beside the last chains; the call's one full
+  // synchronisation follows.  0: the pass after that synchronisation, as before
+  int exact_early = 1;
+  bool want_early = false;  // set by eval_loss_submit around its run_batch
+  bool early_last = false;  // the last run_batch copied the flags early (and left the results' copy to the caller)
+  hipEvent_t ev_flags = nullptr;
+  hipEvent_t ev_red[kMaxChunks] = {};  // chunk c's loss launches and reduces have ended
+  hipStream_t stream3 = nullptr;       // the early exact-sum pass's, created on the first such call
+  hipError_t need_stream3() {
+    return stream3 ? hipSuccess : hipStreamCreateWithFlags(&stream3, hipStreamNonBlocking);
+  }
   hipEvent_t ev_join = nullptr;
   hipEvent_t ev_start = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_end = nullptr;
   hipEvent_t ev_c0[kMaxChunks] = {}, ev_c1[kMaxChunks] = {};  // per-chunk interpreter launches
@@ -690,6 +709,9 @@ struct BatchCall {
   int64_t fold_n_terms = 0;
   FoldPlan fold;
   bool fold_cand = false, fold_compact = false;
+  // plan_chunks: the chunks' bounds
+  ChunkPlan cplan;
+  bool early = false;  // the flags go to pinned memory behind the last chunk's reduce (sr_ctx::exact_early)
   bool host_out = false, fold_mirror = false, host_red = false, use_hint = false, use_probe = false, stress_probe = false;
   // launch_derived: the derived-column spec and map, the columns' leading dimension, the call's leaf bound
   std::vector<int16_t> dmap;
@@ -820,7 +842,6 @@ struct BatchCall {
       if (g_vs.lds > kLdsMax) Rv = 0;
     }
     ctx->rows_last = Rv > 0 ? Rv : R;  // (every C2-like tree fits the register stack)
-    n_chunks = sr_chunk_count(nt, ctx->chunks, ctx->first_chunk, ctx->chunk_min, multi, mode);
     g_ls = gs.grid(nt > 0 ? nt : 1, R, 1);
     glast = g_ls;
     n_rb = g_ls.n_row_blocks;
@@ -922,6 +943,21 @@ struct BatchCall {
     return SR_OK;
   }
 
+  // The chunks of the call (sr_plan.h), after the fold's path: a plain path-2 call whose loss launch composes
+  // candidates takes the three-chunk schedule (sr_ctx::tail_chunk; a view below the register-stack kernel's
+  // 2^17 rows has no such launch and keeps two chunks), every other call the two-chunk pipeline; and whether
+  // the flags go back early (sr_ctx::exact_early).
+  int plan_chunks() {
+    cplan = sr_chunk_plan(nt, ctx->chunks, ctx->first_chunk, ctx->chunk_min, multi, mode,
+                          fold_compact && fold_cand && Rv == 16 ? ctx->tail_chunk : 0);  // (Rv 16: launch_region's cand_launch)
+    n_chunks = cplan.n;
+    early = ctx->exact_early && ctx->want_early && fold.path != 0 && n_chunks > 1 && !multi && !shard && !parametric &&
+            mode == SR_MODE_LOSS;
+    if (early) SR_HIP_CHECK(ctx->need_stream3());
+    if (!ctx->internal_pass) ctx->early_last = early;
+    return SR_OK;
+  }
+
   // The call's results: {Σ loss | flags | the fold's values | their status}, one allocation (one DMA back),
   // on the device or — the latency path — in pinned host memory; the PRED rows.
   int bind_outputs() {
@@ -940,7 +976,7 @@ struct BatchCall {
     // (other stored-loss folds of a small call: Σ and flags stay on the device for the pair kernel, and the
     //  walk copies them to pinned memory beside the fold's values — no copy back, SrFoldWho::msum)
     fold_mirror = small_call && ctx->host_io >= 1 && ctx->want_host_out && fold.path == 1 && !fold_small && !shard;
-    if (host_out || fold_mirror) SR_HIP_CHECK(ctx->h_outs.ensure(outs_bytes, s, ctx->stream2));
+    if (host_out || fold_mirror || early) SR_HIP_CHECK(ctx->h_outs.ensure(outs_bytes, s, ctx->stream2));
     ctx->outs_on_host = host_out || fold_mirror;
     host_red = host_out && ctx->host_reduce > 0 && !multi && n_rb > 1 && int64_t(n_part) <= ctx->host_reduce;
     ctx->host_reductions.clear();
@@ -1117,8 +1153,8 @@ struct BatchCall {
   // Chunk c's bounds, stream and compiled programs.
   int compile_chunk(BatchChunk<T>& ch) {
     static const bool phase_debug = std::getenv("SR_AMD_PHASE_DEBUG") != nullptr;  // (latency analysis)
-    const int64_t t0 = ch.t0 = sr_chunk_bound(ch.c, n_chunks, nt, ctx->first_chunk);
-    const int64_t nc = ch.nc = sr_chunk_bound(ch.c + 1, n_chunks, nt, ctx->first_chunk) - t0;
+    const int64_t t0 = ch.t0 = cplan.bound[ch.c];
+    const int64_t nc = ch.nc = cplan.bound[ch.c + 1] - t0;
     for (int64_t t = t0; t < t0 + nc; ++t)
       ch.max_nodes = std::max<uint32_t>(ch.max_nodes, uint32_t(trees->offsets[t + 1] - trees->offsets[t]));
     // chunks alternate between two streams: chunk c+1's workgroups fill the GPU while chunk c drains
@@ -1460,6 +1496,13 @@ struct BatchCall {
     if (ch.n_vs > 0) SR_STAGE(launch_region(ch, 0, ch.n_vs, true));
     if (ch.n_vs < ch.nc) SR_STAGE(launch_region(ch, ch.n_vs, ch.nc - ch.n_vs, false));
     if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_c1[c], ch.cs));
+    if (early) SR_HIP_CHECK(hipEventRecord(ctx->ev_red[c], ch.cs));
+    if (early && c == n_chunks - 1) {  // every chunk's flags are final: to pinned memory, ahead of this chunk's chain
+      for (int k = 0; k < c; ++k) SR_HIP_CHECK(hipStreamWaitEvent(ch.cs, ctx->ev_red[k], 0));
+      SR_HIP_CHECK(hipMemcpyAsync(ctx->h_outs.as<char>() + ctx->outs_flag_off, ctx->outs.as<char>() + ctx->outs_flag_off,
+                                  size_t(nt) * sizeof(uint32_t), hipMemcpyDeviceToHost, ch.cs));
+      SR_HIP_CHECK(hipEventRecord(ctx->ev_flags, ch.cs));
+    }
     if (fold.path && !shard && !fjob.regions.empty()) SR_STAGE(fold_chunk(ch));
     ctx->n_chunks_last = c + 1;
     code_base += uint32_t(ch.ncode);
@@ -1474,6 +1517,7 @@ struct BatchCall {
     SR_STAGE(bind_buffers());
     in_flight = true;  // (plan_fold's memset is the call's first asynchronous operation)
     SR_STAGE(plan_fold());
+    SR_STAGE(plan_chunks());
     SR_STAGE(bind_outputs());
     SR_STAGE(prepare_hints());
     SR_STAGE(begin_programs());
@@ -2304,6 +2348,7 @@ struct LossCall {
   ViewSpec views{};
   SrProgramBatch<T> prog;
   std::chrono::steady_clock::time_point t0;
+  bool early = false;  // run_batch copied the flags early (sr_ctx::exact_early): finish copies the results back
 };
 template <typename T>
 int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c);
@@ -2335,13 +2380,18 @@ int eval_loss_submit(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_t
   Grid g;
   ctx->want_host_out = true;
   ctx->want_fold = true;
+  ctx->want_early = true;
+  ctx->early_last = false;
   int rc = run_batch<T>(ctx, ds, opset_id, trees, row_idx, n_idx, n_eval, loss_kind, SR_MODE_LOSS, &prog, &g, true,
                         nullptr, views);
   ctx->want_host_out = false;
   ctx->want_fold = false;
+  ctx->want_early = false;
   if (rc != SR_OK) return rc;
   if (nt == 0) return SR_OK;
   hipStream_t s = ctx->stream;
+  c->early = ctx->early_last;
+  if (c->early) return SR_OK;  // (eval_loss_finish: the exact-sum pass first, then the one copy back)
   // {Σ loss, flags} of every tree: already in pinned memory (host_io), or one DMA there
   if (!ctx->outs_on_host) {
     const size_t out_bytes = ctx->fold_path_last ? ctx->outs_bytes_all : ctx->outs_flag_off + size_t(nt) * sizeof(uint32_t);
@@ -2374,21 +2424,74 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
   hipStream_t s = ctx->stream;
   int rc = SR_OK;
 
-  SR_HIP_CHECK(hipStreamSynchronize(s));
-  if (!ctx->host_reductions.empty()) host_reduce_partials(ctx, nt);
   const double* hs = ctx->h_outs.as<double>();
   const uint32_t* hf = reinterpret_cast<const uint32_t*>(ctx->h_outs.as<char>() + ctx->outs_flag_off);
+  auto big_list = [&](const uint32_t* fl, std::vector<int64_t>* out) {
+    for (int64_t t = 0; t < nt; ++t)
+      if ((fl[t] & (SR_FLAG_NONFINITE | SR_FLAG_STATIC)) == 0 && (fl[t] & SR_FLAG_BIG)) out->push_back(t);
+  };
+  std::vector<int64_t> list;
+  std::vector<uint8_t> list_ok;
+  bool exact_done = false;
+  if (c.early) {
+    // (sr_ctx::exact_early) the flags are in pinned memory once ev_flags has fired — the last chunk's chain
+    // still runs; the BIG trees' exact-sum pass is enqueued beside it, then the results' copy behind every
+    // stream, and one synchronisation covers both
+    rc = [&]() -> int {
+      SR_HIP_CHECK(hipEventSynchronize(ctx->ev_flags));
+      ctx->mark_phase(2);
+      big_list(hf, &list);
+      list_ok.assign(list.size(), 1);
+      ctx->n_exact_last = int64_t(list.size());
+      ctx->exact_kernel_ms = 0.0;
+      int mc = 0;
+      for (int64_t t : list) mc = std::max(mc, int(prog.n_checks[size_t(t)]));
+      const std::vector<JlRange>& ranges = jl_ranges_cached(n_eval);
+      // (one batch of the pass; a longer list — never seen — takes the pass after the synchronisation)
+      const bool one_batch = mc > 0 && !ranges.empty() &&
+                             list.size() <= std::max<size_t>(1, (size_t(256) << 20) / (size_t(mc) * ranges.size() * sizeof(T)));
+      std::vector<uint8_t> fin(list.size() * size_t(std::max(mc, 1)));
+      size_t fin_off = 0;
+      hipStream_t xs = ctx->stream3;  // (no chain occupies it)
+      if (one_batch) {
+        SR_STAGE(run_exact<T>(ctx, ds, prog, row_idx, n_idx, list.data(), int64_t(list.size()), mc, ranges, nullptr,
+                              fin.data(), 0, xs, false, &fin_off));
+        SR_HIP_CHECK(hipEventRecord(ctx->ev_join, xs));
+        SR_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0));
+      }
+      SR_HIP_CHECK(hipMemcpyAsync(ctx->h_outs.p, ctx->outs.p, ctx->outs_bytes_all, hipMemcpyDeviceToHost, s));
+      SR_HIP_CHECK(hipStreamSynchronize(s));
+      if (one_batch) {
+        const uint8_t* f = reinterpret_cast<const uint8_t*>(ctx->h_exact.as<char>() + fin_off);
+        for (size_t i = 0; i < list.size(); ++i)
+          for (int k = 0; k < mc; ++k) list_ok[i] &= f[i * size_t(mc) + size_t(k)];
+        float km = 0.f;
+        if (hipEventElapsedTime(&km, ctx->ev_k0, ctx->ev_k1) == hipSuccess) ctx->exact_kernel_ms += double(km);
+      }
+      exact_done = one_batch || mc == 0;
+      return SR_OK;
+    }();
+    if (rc != SR_OK) {  // no launch or DMA of the call may outlive it
+      (void)hipStreamSynchronize(s);
+      if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+      if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
+      return rc;
+    }
+  } else {
+    SR_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  if (!ctx->host_reductions.empty()) host_reduce_partials(ctx, nt);
   std::vector<double> sums(hs, hs + nt);
   std::vector<uint32_t> flags(hf, hf + nt);
   ctx->timing_pending = true;
-  ctx->mark_phase(2);
-  std::vector<int64_t> list;
-  for (int64_t t = 0; t < nt; ++t)
-    if ((flags[t] & (SR_FLAG_NONFINITE | SR_FLAG_STATIC)) == 0 && (flags[t] & SR_FLAG_BIG)) list.push_back(t);
-  std::vector<uint8_t> list_ok(list.size(), 1);
-  ctx->n_exact_last = int64_t(list.size());
-  ctx->exact_kernel_ms = 0.0;
-  for (int v = 0; v < n_views && !list.empty(); ++v) {  // (each view's listed trees over its own rows)
+  if (!c.early) {
+    ctx->mark_phase(2);
+    big_list(flags.data(), &list);
+    list_ok.assign(list.size(), 1);
+    ctx->n_exact_last = int64_t(list.size());
+    ctx->exact_kernel_ms = 0.0;
+  }
+  for (int v = 0; v < n_views && !list.empty() && !exact_done; ++v) {  // (each view's listed trees over its own rows)
     std::vector<int64_t> lv;
     std::vector<size_t> at;
     for (size_t i = 0; i < list.size(); ++i)
@@ -3791,9 +3894,14 @@ int sr_init(int device, sr_ctx** out) {
   if (const char* v = std::getenv("SR_AMD_FOLD_COMPACT")) ctx->fold_compact = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST")) ctx->fold_cand_est = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST_MIN")) ctx->fold_cand_est_min = std::max(1, std::atoi(v));
+  if (const char* v = std::getenv("SR_AMD_TAIL_CHUNK")) ctx->tail_chunk = std::max(0, std::min(kTailTwelfths, std::atoi(v)));
+  if (const char* v = std::getenv("SR_AMD_EXACT_EARLY")) ctx->exact_early = std::atoi(v) != 0 ? 1 : 0;
   hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e == hipSuccess && std::getenv("SR_AMD_EAGER_STREAM2")) e = ctx->need_stream2();  // (A/B: the round-4 layout)
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_flags, hipEventDisableTiming);
+  for (int c = 0; c < kMaxChunks; ++c)
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_red[c], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev_start);
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev_k0);
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev_k1);
@@ -3853,6 +3961,12 @@ int sr_shutdown(sr_ctx* ctx) {
     }
     for (hipEvent_t ev : ctx->ev_f) (void)hipEventDestroy(ev);
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+    if (ctx->stream3) {
+      (void)hipStreamSynchronize(ctx->stream3);
+      (void)hipStreamDestroy(ctx->stream3);
+    }
+    (void)hipEventDestroy(ctx->ev_flags);
+    for (int c = 0; c < kMaxChunks; ++c) (void)hipEventDestroy(ctx->ev_red[c]);
     (void)hipEventDestroy(ctx->ev_join);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     (void)hipEventDestroy(ctx->ev_start);
@@ -4619,6 +4733,15 @@ int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value) {
   }
   if (std::strcmp(name, "fold_compact") == 0) {  // the FOLD pass over per-row-block work lists (SR_AMD_FOLD_COMPACT)
     ctx->fold_compact = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "tail_chunk") == 0) {  // the last of three chunks of a plain path-2 call, in twelfths (SR_AMD_TAIL_CHUNK)
+    if (value < 0 || value > kTailTwelfths) return set_error(SR_ERR_INVALID_ARG, "tail_chunk: 0, or the last chunk's twelfths 1..6");
+    ctx->tail_chunk = int(value);
+    return SR_OK;
+  }
+  if (std::strcmp(name, "exact_early") == 0) {  // the exact-sum pass beside the last fold chains (SR_AMD_EXACT_EARLY)
+    ctx->exact_early = value != 0 ? 1 : 0;
     return SR_OK;
   }
   if (std::strcmp(name, "fold_cand_est") == 0) {  // the candidates' guess from the running prefix (SR_AMD_FOLD_CAND_EST)

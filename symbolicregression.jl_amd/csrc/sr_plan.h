@@ -189,6 +189,38 @@ inline int64_t sr_chunk_bound(int k, int n_chunks, int64_t nt, int first_chunk) 
   if (k >= n_chunks) return nt;
   return n_chunks == 2 ? nt / first_chunk : nt * k / n_chunks;
 }
+// A call's chunks: bound[k] = first tree of chunk k, bound[n] = the tree count.
+struct ChunkPlan {
+  int n = 1;
+  int64_t bound[kMaxChunks + 1] = {0, 0, 0, 0, 0};
+};
+// The three-chunk schedule (sr_ctx::tail_chunk; the caller passes tail = 0 for every call but a plain
+// single-GPU path-2 call whose loss launch composes candidates: a fold chain — plan, compact, scan, FOLD
+// re-run, walk — follows each chunk's loss launch on the chunk's stream): {1 / first_chunk, the rest,
+// tail / 12} of the trees (tail 1..6).  The first chunk still hides the compile; the other two loss launches
+// share the GPU and end close together, so their chains, which are latency-bound, run side by side
+// instead of one chain over 5/6 of the trees alone.  Every chunk holds at least chunk_min trees, else — and
+// with tail = 0, or chunks != 2 — the bounds are sr_chunk_count / sr_chunk_bound's exactly.
+constexpr int kTailTwelfths = 6;
+inline ChunkPlan sr_chunk_plan(int64_t nt, int chunks, int first_chunk, int64_t chunk_min, bool multi, int mode,
+                               int tail) {
+  ChunkPlan p;
+  const int a = tail > 0 ? std::min(tail, kTailTwelfths) : 0;
+  if (a > 0 && !multi && mode == SR_MODE_LOSS && chunks == 2 && nt > 0) {
+    const int64_t lo = std::max<int64_t>(chunk_min, 1);
+    const int64_t first = nt / first_chunk, last = nt * a / 12;
+    if (first >= lo && last >= lo && nt - first - last >= lo) {
+      p.n = 3;
+      p.bound[1] = first;
+      p.bound[2] = nt - last;
+      p.bound[3] = nt;
+      return p;
+    }
+  }
+  p.n = sr_chunk_count(nt, chunks, first_chunk, chunk_min, multi, mode);
+  for (int k = 0; k <= p.n; ++k) p.bound[k] = sr_chunk_bound(k, p.n, nt, first_chunk);
+  return p;
+}
 
 // ---------------------------------------------------------------- the staging image
 // programs + per-tree metadata of a call: ONE device allocation and ONE pinned staging buffer with the

@@ -3,7 +3,7 @@
 //
 // Build and run through `make -C symbolicregression.jl_amd plan-check`, which compiles this file with
 // -fsanitize=address,undefined.  It checks the grids (values derived by hand from make_grid, and its
-// invariants over a sweep), the chunk bounds, a chunk's launch order (counting sort, the deal over tree
+// invariants over a sweep), the chunk bounds (the two-chunk pipeline and the three-chunk schedule), a chunk's launch order (counting sort, the deal over tree
 // groups, views), the code layout, the view segments, the longest group span and the in-order fold's path
 // decision.  Exit status 0 and "plan_check: ok" on success.
 #include <cstdint>
@@ -101,6 +101,41 @@ void check_chunks() {
   CHECK(sr_chunk_count(10000, 4, 6, 1024, true, SR_MODE_LOSS) == 1);
   CHECK(sr_chunk_count(10000, 2, 6, 1024, false, SR_MODE_PRED) == 1);  // PRED writes rows by caller tree index
   CHECK(sr_chunk_count(10000, 1, 6, 1024, false, SR_MODE_LOSS) == 1);
+  // the three-chunk schedule (sr_chunk_plan): C2's 10,000 trees
+  {
+    const ChunkPlan p = sr_chunk_plan(10000, 2, 6, 1024, false, SR_MODE_LOSS, 4);  // {1/6, 1/2, 1/3}
+    CHECK(p.n == 3 && p.bound[0] == 0 && p.bound[1] == 1666 && p.bound[2] == 10000 - 3333 && p.bound[3] == 10000);
+    CHECK(sr_chunk_plan(6600, 2, 6, 1024, false, SR_MODE_LOSS, 1).n == 2);   // (a last chunk of 550 < chunk_min)
+    CHECK(sr_chunk_plan(1204, 2, 6, 64, false, SR_MODE_LOSS, 4).n == 3);
+    CHECK(sr_chunk_plan(1204, 2, 2, 64, false, SR_MODE_LOSS, 6).n == 2);     // (nothing left for the middle chunk)
+  }
+  // ... over every tree count to a few thousand and every chunk_min / first_chunk / tail_chunk the knobs allow
+  // (chunk_min sampled): monotone bounds that cover [0, nt], at most kMaxChunks chunks, none but the only one
+  // below chunk_min, the first chunk 1 / first_chunk; and with tail 0 — every call outside the schedule's
+  // rule — sr_chunk_count / sr_chunk_bound exactly
+  for (int64_t nt = 0; nt <= 3000; nt += (nt < 300 ? 1 : 7))
+    for (int first_chunk : {2, 3, 6, 7, 12, 64})
+      for (int64_t chunk_min : {int64_t(1), int64_t(2), int64_t(64), int64_t(100), int64_t(1024), int64_t(5000)})
+        for (int chunks : {1, 2, 3, 4, 8})
+          for (int mode : {int(SR_MODE_LOSS), int(SR_MODE_PRED)})
+            for (int multi = 0; multi <= 1; ++multi)
+              for (int tail = 0; tail <= kTailTwelfths; ++tail) {
+                const ChunkPlan p = sr_chunk_plan(nt, chunks, first_chunk, chunk_min, multi != 0, mode, tail);
+                const int n_old = sr_chunk_count(nt, chunks, first_chunk, chunk_min, multi != 0, mode);
+                CHECK(p.n >= 1 && p.n <= kMaxChunks && p.bound[0] == 0 && p.bound[p.n] == nt);
+                for (int k = 0; k < p.n; ++k) {
+                  CHECK(p.bound[k] <= p.bound[k + 1]);
+                  if (p.n > 1 && chunks == 2) CHECK(p.bound[k + 1] - p.bound[k] >= chunk_min);
+                }
+                const bool old = tail == 0 || chunks != 2 || multi || mode != SR_MODE_LOSS || p.n != 3;
+                if (old) {
+                  CHECK(p.n == n_old);
+                  for (int k = 0; k <= p.n; ++k) CHECK(p.bound[k] == sr_chunk_bound(k, n_old, nt, first_chunk));
+                } else {
+                  CHECK(n_old == 2 && p.bound[1] == nt / first_chunk);  // (the first chunk hides the compile)
+                  CHECK(p.bound[3] - p.bound[2] == nt * tail / 12);
+                }
+              }
   // the staging image: code | offsets | static_bad | order | ends | segments, each part 256-byte aligned
   // and large enough for its array
   for (int64_t nt : {0, 1, 63, 1000})
