@@ -498,8 +498,10 @@ int sr_last_kernel_ms(sr_ctx* ctx, double* eval_ms, double* total_ms);
  * the reference's T-precision fold: csrc/sr_fold.h), out[10] (n >= 11) = the segments of those folds
  * folded row by row (the rest advanced by their composed steps), out[11] (n >= 12) = the fold's
  * segment length in rows (0: one scan over every row), out[12..15] (n >= 16) = the fold's device time
- * (ms, HIP events, summed over its batches) in its PRED pass, segment sums, composed steps and chain.  sr_last_kernel_ms's eval_ms is the sum of
- * those launches' durations. */
+ * (ms, HIP events, summed over its batches) in its PRED pass, segment sums, composed steps and chain,
+ * out[16..18] (n >= 19) = the call's listed loss launches ("loss_compact" below), and over them the launch
+ * positions listed and the ones excluded (read back from the device once per call, on request).
+ * sr_last_kernel_ms's eval_ms is the sum of those launches' durations. */
 int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
 
 /* Run-time tuning of a context (the SR_AMD_* environment variables are read once at sr_init):
@@ -526,7 +528,11 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * "fold_cand_est_min" of them have, 4 by default; 0: from the block's first tile alone; `taken` and `rerun`
  * of sr_last_fold_cand then vary from run to run, their sum and every result do not), "fold_compact" (1, the
  * default: the FOLD pass of a plain path-2 call runs over per-row-block lists of the positions left to it;
- * 0: over the loss launch's grid), "tail_chunk" (4, the default: such a call whose loss launch composes
+ * 0: over the loss launch's grid), "loss_compact" (1, the default: the candidate-composing loss launch of such
+ * a call runs over the launch positions its chunk's dead-tree probe left alive, G per workgroup, and the reduce
+ * writes the others' result — non-finite — without reading a partial; 0: over every position),
+ * "loss_list_groups" (0, the default: that list is dealt over all of the launch's tree groups; n: over at most n),
+ * "tail_chunk" (4, the default: such a call whose loss launch composes
  * candidates runs three tree chunks — 1 / "first_chunk", the rest, the last value/12 of the trees (1..6), each
  * of at least "chunk_min" trees — whose last two fold chains run side by side; 0: the two-chunk pipeline),
  * "exact_early" (1, the default: a multi-chunk call under the fold copies its flags to pinned memory behind

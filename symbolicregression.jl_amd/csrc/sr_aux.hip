@@ -788,6 +788,107 @@ hipError_t sr_launch_fold_compact(const SrFoldTabs& ft, int np, int n_rb, int G,
   return hipGetLastError();
 }
 
+// The listed loss launch's work list (SrEvalArgs::fold_list in a SR_TIER_CAND loss launch): the dead-tree
+// probe has marked most incomplete trees by launch position before the chunk's loss launch starts, and a
+// launch over every position gives each wave a third of its slots to run (C2) while every workgroup still
+// stages its tiles.  One workgroup keeps, in launch order (stable: the cost ordering still reaches the
+// waves), the positions whose hint is not this call's epoch and whose tree is not statically incomplete (an
+// empty program no wave runs: C2 has 1,814, which would fill a third of the list's slots): list[0 .. cnt[0]);
+// excl[p] = 1 for the others, whose results the reduce writes without reading a partial
+// (sr_reduce_partials_excl_kernel).
+// It also deals the list over workgroups: cnt = {n_live, g, n_groups}, g entries per workgroup and n_groups =
+// ceil(n_live / g) workgroups per row block.  Not simply the launch's G: the fewer tree groups a launch has,
+// the more row blocks its ~1,024 resident workgroups span, and the candidates' guess from the running prefix
+// (SrEvalArgs::fold_est_sum) lags by that many row blocks — with a third of the groups, a tree's first ~100
+// row blocks would fall back to the first-tile guess and the FOLD pass would run them again.  So the list is
+// dealt over all of the grid's tree groups (grid_groups: the region's, the bound on n_groups; want_groups > 0:
+// over at most that many), g a multiple of the 4 waves, at least min(G, 32) and at most G: as many
+// workgroups as the full launch's, each with fewer, live trees, dealt evenly over its waves.
+__global__ void __launch_bounds__(256) sr_loss_compact_kernel(const uint32_t* __restrict__ hint, uint32_t epoch, int np,
+                                                              const uint32_t* __restrict__ perm,
+                                                              const uint8_t* __restrict__ static_bad,
+                                                              int G, int grid_groups, int want_groups,
+                                                              int32_t* __restrict__ list, int32_t* __restrict__ cnt,
+                                                              uint8_t* __restrict__ excl) {
+  __shared__ int s_w[4];
+  const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  int base = 0;  // (uniform: the entries kept so far)
+  for (int p0 = 0; p0 < np; p0 += 256) {
+    const int p = p0 + tid;
+    const bool keep = p < np && hint[p] != epoch && !static_bad[perm ? perm[p] : uint32_t(p)];
+    const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
+    if (lane == 0) s_w[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_w[w];
+      before += w < wave ? c : 0;
+      total += c;
+    }
+    if (keep) list[base + before + __popcll(m & ((uint64_t(1) << lane) - 1u))] = p;
+    if (p < np) excl[p] = keep ? 0 : 1;
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int target = (want_groups > 0 && want_groups < grid_groups) ? want_groups : grid_groups;
+    int g = ((base + target - 1) / target + 3) & ~3;  // (ceil(n_live / target) <= g: at most `target` groups)
+    const int g_min = G < 32 ? G : 32;
+    g = g < g_min ? g_min : (g > G ? G : g);
+    cnt[0] = base;
+    cnt[1] = g;
+    cnt[2] = (base + g - 1) / g;
+  }
+}
+hipError_t sr_launch_loss_compact(const uint32_t* hint, uint32_t epoch, int np, const uint32_t* perm,
+                                  const uint8_t* static_bad, int G, int grid_groups, int want_groups, int32_t* list,
+                                  int32_t* cnt, uint8_t* excl, hipStream_t s) {
+  // (the grid's groups are enough for every position: n_groups <= grid_groups then; a wave has 64 slots)
+  if (np <= 0 || hint == nullptr || static_bad == nullptr || G < 1 || G > 256 ||
+      int64_t(grid_groups) * int64_t(G) < int64_t(np))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sr_loss_compact_kernel, dim3(1), dim3(256), 0, s, hint, epoch, np, perm, static_bad, G, grid_groups,
+                     want_groups, list, cnt, excl);
+  return hipGetLastError();
+}
+// The reduce launch behind a listed loss launch: sr_reduce_partials_kernel for the listed positions; an
+// excluded one gets what the full launch's partials reduce to — every row block skipped it at its first
+// tile, or ran no program: Σ 0, SR_FLAG_NONFINITE (SR_FLAG_STATIC where static_bad) — and none of its partials, which this call did not
+// write, is read.
+__global__ void __launch_bounds__(256) sr_reduce_partials_excl_kernel(const double* __restrict__ part_sum,
+                                                                       const uint32_t* __restrict__ part_flag,
+                                                                       int n_trees, int n_row_blocks,
+                                                                       const uint32_t* __restrict__ perm,
+                                                                       const uint8_t* __restrict__ static_bad,
+                                                                       const uint8_t* __restrict__ excl,
+                                                                       double* __restrict__ out_sum,
+                                                                       uint32_t* __restrict__ out_flag) {
+  const int lane = int(threadIdx.x) & 63;
+  const int pos = int(int64_t(blockIdx.x) * (blockDim.x / 64) + threadIdx.x / 64);
+  if (pos >= n_trees) return;  // wave-uniform
+  if (excl[pos]) {
+    if (lane == 0) {
+      const int tree = perm ? int(perm[pos]) : pos;
+      out_sum[tree] = 0.0;
+      out_flag[tree] = SR_FLAG_NONFINITE | ((static_bad && static_bad[tree]) ? SR_FLAG_STATIC : 0u);
+    }
+    return;
+  }
+  sr_reduce_positions<1, false>(part_sum, part_flag, n_trees, n_row_blocks, pos, 1, 1, perm, static_bad, out_sum,
+                                out_flag, lane);
+}
+hipError_t sr_launch_reduce_excl(const double* part_sum, const uint32_t* part_flag, int n_trees, int n_row_blocks,
+                                 const uint32_t* perm, const uint8_t* static_bad, const uint8_t* excl, double* out_sum,
+                                 uint32_t* out_flag, hipStream_t s) {
+  if (n_trees <= 0) return hipSuccess;
+  if (excl == nullptr) return hipErrorInvalidValue;
+  const int64_t blocks = (int64_t(n_trees) + 3) / 4;  // 4 waves (trees) per block
+  hipLaunchKernelGGL(sr_reduce_partials_excl_kernel, dim3(unsigned(blocks)), dim3(256), 0, s, part_sum, part_flag,
+                     n_trees, n_row_blocks, perm, static_bad, excl, out_sum, out_flag);
+  return hipGetLastError();
+}
+
 // The fold's first rows one by one (Statistics.mean / Base.sum over a generator: the first loss starts
 // the fold), in the hardware's own adds — the running value leaves a binade every few rows here, so a
 // round per crossing would cost ~1 us each.  Rows [0, ks), ks <= 256, of a stored segment b; one wave

@@ -349,6 +349,24 @@ struct sr_ctx {
   int fold_compact = 1;
   DevBuf fold_list;          // [row block][position] int32, laid out as the partials
   DevBuf fold_wg;            // per region (2 per chunk): {cnt [n_rb], wg0 [n_rb + 1]}
+  // SR_AMD_LOSS_COMPACT / "loss_compact": the candidate-composing loss launch of such a call runs over the
+  // launch positions its chunk's dead-tree probe left alive, less the statically incomplete trees
+  // (sr_loss_compact_kernel: one list per launch, dealt over the launch's tree groups, the live workgroups
+  // first), and the reduce gives the excluded positions their result without reading a partial (0: every
+  // position, the launch sequence before the list).
+  int loss_compact = 1;
+  // SR_AMD_LOSS_LIST_GROUPS / "loss_list_groups": the most tree groups a listed launch deals its list over (0,
+  // the default: all of its grid's; sr_loss_compact_kernel: fewer groups = fewer workgroups to stage tiles,
+  // but the candidates' guess from the running prefix lags by resident workgroups / groups row blocks, and
+  // which of a call's overlapping launches ends last moves with it: DESIGN.md §12)
+  int loss_list_groups = 0;
+  DevBuf loss_list;          // {list int32 [nt] | cnt int32 [kMaxChunks][4] | excl uint8 [nt]} (sr_plan.h)
+  // the last call's listed launches: per chunk the launch's positions (0: not listed), and the counters read
+  // back once on request (sr_last_phase_ms out[16..18])
+  int64_t loss_listed_np[kMaxChunks] = {0, 0, 0, 0};
+  int64_t loss_list_nt_last = 0;
+  bool loss_list_read = true;
+  int64_t n_loss_listed_launches_last = 0, n_loss_live_last = 0, n_loss_excl_last = 0;
   // SR_AMD_FOLD_CAND_EST / "fold_cand_est": the candidates' guess from the tree's running prefix (the row
   // blocks other workgroups have finished; 0: the block's first tile only); usable from fold_cand_est_min
   // finished blocks on (SR_AMD_FOLD_CAND_EST_MIN; tools/fold_cand_sim.py)
@@ -589,6 +607,9 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
   fa.fold_cand = nullptr;
   fa.fold_est_sum = nullptr;
   fa.fold_est_cnt = nullptr;
+  fa.fold_list = nullptr;  // (a listed loss launch's list is not the FOLD pass's)
+  fa.fold_cnt = nullptr;
+  fa.fold_wg0 = nullptr;
   // the compacted launch (sr_ctx::fold_compact): plain single-GPU calls over the full view; the grid stays the
   // region's (an upper bound: the list's workgroups come first, the rest return at once)
   if (ctx->fold_compact && fr.idx >= 0 && !fr.p.ptab && !job.gather && fr.a.segs == nullptr && who.elig == nullptr &&
@@ -708,7 +729,7 @@ struct BatchCall {
   // plan_fold / bind_outputs / prepare_hints
   int64_t fold_n_terms = 0;
   FoldPlan fold;
-  bool fold_cand = false, fold_compact = false;
+  bool fold_cand = false, fold_compact = false, loss_compact = false;
   // plan_chunks: the chunks' bounds
   ChunkPlan cplan;
   bool early = false;  // the flags go to pinned memory behind the last chunk's reduce (sr_ctx::exact_early)
@@ -934,7 +955,14 @@ struct BatchCall {
       SR_HIP_CHECK(ctx->fold_list.ensure(n_part * sizeof(int32_t) + 4));
       SR_HIP_CHECK(ctx->fold_wg.ensure(sr_fold_wg_words(n_rb) * sizeof(int32_t)));
     }
+    // the listed loss launch (sr_ctx::loss_compact): the calls that take both of the above
+    loss_compact = fold_compact && fold_cand && ctx->loss_compact && mode == SR_MODE_LOSS;
+    if (loss_compact) SR_HIP_CHECK(ctx->loss_list.ensure(sr_loss_list_bytes(nt)));
     if (!ctx->internal_pass) {  // (the fallback's prediction passes leave the call's record alone)
+      for (int c = 0; c < kMaxChunks; ++c) ctx->loss_listed_np[c] = 0;
+      ctx->loss_list_nt_last = nt;
+      ctx->loss_list_read = true;
+      ctx->n_loss_listed_launches_last = ctx->n_loss_live_last = ctx->n_loss_excl_last = 0;
       ctx->fold_path_last = fold.path;
       ctx->fold_timed_last = false;
       ctx->fold_cand_read = fold.path != 2;
@@ -1431,8 +1459,8 @@ struct BatchCall {
     // (round 5, later: also the first of two chunks when it is that large — C4's 8M-row shard
     //  216.9 -> 214.4 ms per call, C2 unchanged; tools/c4_shard_probe.py, profiles/r05_ab_c4_shard.txt)
     const bool probe_first = ch.nc >= 512 && n_eval >= (int64_t(1) << 18);
-    if (use_probe && p0 == 0 && g.n_row_blocks >= 16 && (ctx->probe != 2 || ch.c > 0 || probe_first))
-      SR_STAGE(launch_probe(ch, a, pa_, np, g));
+    const bool probed = use_probe && p0 == 0 && g.n_row_blocks >= 16 && (ctx->probe != 2 || ch.c > 0 || probe_first);
+    if (probed) SR_STAGE(launch_probe(ch, a, pa_, np, g));
 #ifdef SR_STAMPS
     ctx->n_stamps = g.n_blocks * g.W * SR_NSTAMPS;
     SR_HIP_CHECK(ctx->stamps.ensure(size_t(ctx->n_stamps) * sizeof(uint64_t)));
@@ -1448,6 +1476,28 @@ struct BatchCall {
       a.fold_est_cnt = reinterpret_cast<uint32_t*>(ctx->fold_est.as<double>() + nt) + t0 + p0;
       a.fold_est_min = uint32_t(ctx->fold_cand_est_min);
     }
+    // the listed launch (sr_ctx::loss_compact): the candidate launch of a region whose probe has just run on
+    // this stream, reduced by a reduce launch; the list from the hints as the probe left them
+    const bool listed = loss_compact && cand_launch && probed && !direct && !fused && !host_red && !fjob.fuse_reduce &&
+                        !parametric && !multi;
+    uint8_t* excl = nullptr;
+    if (listed) {
+      char* const lb = ctx->loss_list.as<char>();
+      int32_t* const list = reinterpret_cast<int32_t*>(lb) + t0 + p0;
+      int32_t* const cnt = reinterpret_cast<int32_t*>(lb + sr_loss_list_cnt_off(nt)) + ch.c * kLossListCnt;
+      excl = reinterpret_cast<uint8_t*>(lb + sr_loss_list_excl_off(nt)) + t0 + p0;
+      SR_HIP_CHECK(sr_launch_loss_compact(a.hint, a.hint_epoch, int(np), a.perm, ctx->d_bad + t0, g.G, g.n_groups,
+                                          ctx->loss_list_groups, list, cnt, excl, cs));
+      a.fold_list = list;
+      a.fold_cnt = cnt;
+      // (a listed group's span takes in the excluded programs between its trees: the whole cache budget, and
+      //  the kernel's own test per workgroup)
+      if (a.code_lds > 0) a.code_lds = int((kCodeCacheLds - size_t(g.lds)) / 16);
+      if (!ctx->internal_pass) {
+        ctx->loss_listed_np[ch.c] = np;
+        ctx->loss_list_read = false;
+      }
+    }
     if (parametric)
       SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
     else if (cand_launch)
@@ -1457,6 +1507,9 @@ struct BatchCall {
     if (fold.path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g, fold_compact ? sr_fold_region(ch.c, vstk) : -1});
     if (!direct && !fused && host_red)
       ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
+    else if (listed)
+      SR_HIP_CHECK(sr_launch_reduce_excl(a.part_sum, a.part_flag, int(np), g.n_row_blocks, a.perm, ctx->d_bad + t0, excl,
+                                         ctx->d_out_sum + t0, ctx->d_out_flag + t0, cs));
     else if (!direct && !fused && !fjob.fuse_reduce)
       SR_HIP_CHECK(sr_launch_reduce(a.part_sum, a.part_flag, int(np), g.n_row_blocks, a.perm, ctx->d_bad + t0,
                                     ctx->d_out_sum + t0, ctx->d_out_flag + t0, cs));
@@ -3892,6 +3945,8 @@ int sr_init(int device, sr_ctx** out) {
   if (const char* v = std::getenv("SR_AMD_FOLD_PRE_START")) ctx->fold_pre_start = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_SINGLE_PASS")) ctx->fold_single_pass = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_COMPACT")) ctx->fold_compact = std::atoi(v) != 0 ? 1 : 0;
+  if (const char* v = std::getenv("SR_AMD_LOSS_COMPACT")) ctx->loss_compact = std::atoi(v) != 0 ? 1 : 0;
+  if (const char* v = std::getenv("SR_AMD_LOSS_LIST_GROUPS")) ctx->loss_list_groups = std::max(0, std::atoi(v));
   if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST")) ctx->fold_cand_est = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST_MIN")) ctx->fold_cand_est_min = std::max(1, std::atoi(v));
   if (const char* v = std::getenv("SR_AMD_TAIL_CHUNK")) ctx->tail_chunk = std::max(0, std::min(kTailTwelfths, std::atoi(v)));
@@ -3945,7 +4000,7 @@ int sr_shutdown(sr_ctx* ctx) {
                       &ctx->hint, &ctx->jsum_prog, &ctx->jsum_scratch, &ctx->probe_sum, &ctx->probe_flag, &ctx->g_code, &ctx->g_offsets, &ctx->g_consts, &ctx->g_const_off,
                       &ctx->g_items, &ctx->g_part, &ctx->g_out, &ctx->derived_cols, &ctx->probe_derived, &ctx->coll_buf, &ctx->coll_packed, &ctx->ctl, &ctx->fold_io, &ctx->group_cnt,
                       &ctx->fold_code, &ctx->fold_tab, &ctx->fold_store, &ctx->fold_ctl, &ctx->fold_io2, &ctx->fold_sq,
-                      &ctx->fold_tab2, &ctx->ptab, &ctx->fold_cand, &ctx->fold_list, &ctx->fold_wg, &ctx->fold_est})
+                      &ctx->fold_tab2, &ctx->ptab, &ctx->fold_cand, &ctx->fold_list, &ctx->fold_wg, &ctx->fold_est, &ctx->loss_list})
       b->release();
     for (HostBuf* b : {&ctx->h_prog, &ctx->h_outs, &ctx->h_grad, &ctx->h_coll, &ctx->h_part, &ctx->h_exact, &ctx->h_ptab})
       b->release();
@@ -4663,6 +4718,23 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n) {
   if (n > 11) out[11] = double(ctx->fold_seg_last);
   for (int i = 0; i < 4; ++i)
     if (n > 12 + i) out[12 + i] = ctx->fold_ms[i];
+  if (n > 16 && !ctx->loss_list_read) {  // (the last call's listed loss launches: their counters, read once)
+    int32_t h[kMaxChunks * kLossListCnt] = {};
+    SR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->stream2) SR_HIP_CHECK(hipStreamSynchronize(ctx->stream2));
+    SR_HIP_CHECK(hipMemcpy(h, ctx->loss_list.as<char>() + sr_loss_list_cnt_off(ctx->loss_list_nt_last), sizeof(h),
+                           hipMemcpyDeviceToHost));
+    for (int c = 0; c < kMaxChunks; ++c) {
+      if (ctx->loss_listed_np[c] <= 0) continue;
+      ++ctx->n_loss_listed_launches_last;
+      ctx->n_loss_live_last += h[c * kLossListCnt];
+      ctx->n_loss_excl_last += ctx->loss_listed_np[c] - h[c * kLossListCnt];
+    }
+    ctx->loss_list_read = true;
+  }
+  if (n > 16) out[16] = double(ctx->n_loss_listed_launches_last);
+  if (n > 17) out[17] = double(ctx->n_loss_live_last);
+  if (n > 18) out[18] = double(ctx->n_loss_excl_last);
   return SR_OK;
 }
 
@@ -4733,6 +4805,14 @@ int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value) {
   }
   if (std::strcmp(name, "fold_compact") == 0) {  // the FOLD pass over per-row-block work lists (SR_AMD_FOLD_COMPACT)
     ctx->fold_compact = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "loss_compact") == 0) {  // the loss launch over the positions the probe left alive (SR_AMD_LOSS_COMPACT)
+    ctx->loss_compact = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "loss_list_groups") == 0) {  // the tree groups a listed launch deals its list over (SR_AMD_LOSS_LIST_GROUPS)
+    ctx->loss_list_groups = int(std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)));
     return SR_OK;
   }
   if (std::strcmp(name, "tail_chunk") == 0) {  // the last of three chunks of a plain path-2 call, in twelfths (SR_AMD_TAIL_CHUNK)

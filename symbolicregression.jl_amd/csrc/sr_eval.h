@@ -166,6 +166,11 @@ struct SrEvalArgs {
   // block rb the launch positions the FOLD pass must run, in launch order, fold_list[rb * n_trees + k],
   // k < fold_cnt[rb]; workgroups fold_wg0[rb] .. fold_wg0[rb + 1] - 1 take G of them each
   // (fold_wg0[n_row_blocks]: the total; workgroups past it return at once).  sr_fold_compact_kernel.
+  // LOSS, the SR_TIER_CAND build's listed launch (NULL: every position): ONE list for the launch, the
+  // positions the dead-tree probe left alive (statically incomplete trees left out too), in launch order, fold_list[k], k < fold_cnt[0]; workgroup b
+  // takes entries [tg g, tg g + g) of row block rb, g = fold_cnt[1] <= G, tg = b % fold_cnt[2], rb = b / that,
+  // and returns at once past the last row block (the grid is the region's); every per-position array
+  // keeps its [row block][position] layout.  sr_loss_compact_kernel.
   const int32_t* fold_list;
   const int32_t* fold_cnt;
   const int32_t* fold_wg0;
@@ -217,6 +222,18 @@ hipError_t sr_launch_derived(const T* X, int64_t ld, const int64_t* row_idx, int
 hipError_t sr_launch_reduce(const double* part_sum, const uint32_t* part_flag, int n_trees, int n_row_blocks,
                             const uint32_t* perm, const uint8_t* static_bad, double* out_sum, uint32_t* out_flag,
                             hipStream_t s);
+// The listed loss launch (SrEvalArgs::fold_list in a SR_TIER_CAND loss launch): the region's np launch
+// positions whose hint is not `epoch` and whose tree (perm[position]) is not static_bad, in launch order,
+// list[0 .. cnt[0]); cnt[1] entries per workgroup, cnt[2] workgroups per row block (the list dealt over the
+// launch's grid_groups groups of G, or over want_groups > 0 of them); excl[p] = 1 for the others.  And
+// the reduce behind it: sr_launch_reduce for the listed positions, Σ 0 | SR_FLAG_NONFINITE (| SR_FLAG_STATIC)
+// for an excluded one.
+hipError_t sr_launch_loss_compact(const uint32_t* hint, uint32_t epoch, int np, const uint32_t* perm,
+                                  const uint8_t* static_bad, int G, int grid_groups, int want_groups, int32_t* list,
+                                  int32_t* cnt, uint8_t* excl, hipStream_t s);
+hipError_t sr_launch_reduce_excl(const double* part_sum, const uint32_t* part_flag, int n_trees, int n_row_blocks,
+                                 const uint32_t* perm, const uint8_t* static_bad, const uint8_t* excl, double* out_sum,
+                                 uint32_t* out_flag, hipStream_t s);
 // isfinite(Julia pairwise sum) of n_arrays arrays from their leaf folds [n_arrays][n_leaves] (T),
 // combined by the post-order program `prog` (leaf index: push; -1: add the top two).
 template <typename T>

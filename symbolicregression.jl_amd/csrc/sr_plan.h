@@ -467,3 +467,13 @@ inline FoldPlan sr_fold_plan(const FoldPlanIn& in) {
 inline int sr_fold_region(int chunk, bool vstk) { return 2 * chunk + (vstk ? 0 : 1); }
 inline size_t sr_fold_wg_off(int region, int64_t n_rb) { return size_t(region) * (2 * size_t(n_rb) + 2); }
 inline size_t sr_fold_wg_words(int64_t n_rb) { return sr_fold_wg_off(2 * kMaxChunks, n_rb); }
+// The listed loss launch (sr_ctx::loss_compact): one buffer for the call, {list int32 [nt] | cnt int32
+// [kMaxChunks][kLossListCnt] | excl uint8 [nt]} — a chunk's register-stack region (its only listed launch)
+// uses the slices at its first launch position and the counters of its chunk {listed, entries per workgroup,
+// workgroups per row block, -}; byte offsets and the call's bytes.
+constexpr int kLossListCnt = 4;
+inline size_t sr_loss_list_cnt_off(int64_t nt) { return size_t(nt) * sizeof(int32_t); }
+inline size_t sr_loss_list_excl_off(int64_t nt) {
+  return sr_loss_list_cnt_off(nt) + size_t(kMaxChunks) * kLossListCnt * sizeof(int32_t);
+}
+inline size_t sr_loss_list_bytes(int64_t nt) { return sr_loss_list_excl_off(nt) + size_t(nt); }

@@ -898,7 +898,13 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   const int64_t* ridx = a.row_idx;  // GATHER: this block's row view
   // FOLD, the compacted launch: the workgroup's row block and its G entries of that block's list (tree0:
   // the first one's index in the list, not a launch position)
+  // LOSS, the candidate build's listed launch (sr_loss_compact_kernel): ONE list for the launch, the positions
+  // the dead-tree probe left alive, in launch order (fold_cnt[0] of them); workgroup = (row block, fold_cnt[1]
+  // list entries), tree group fastest as below, the live workgroups first and dense (the grid is the region's)
+  // (every change for it sits under `if constexpr (CAND)`: the other builds compile the code they had)
   const bool listed = (MODE == SR_MODE_FOLD) && a.fold_list != nullptr;
+  bool loss_listed = false;
+  if constexpr (CAND) loss_listed = a.fold_list != nullptr;
   if (listed) {
     if (int(blockIdx.x) >= a.fold_wg0[a.n_row_blocks]) return;  // (the grid is the loss launch's: an upper bound)
     int lo = 0, hi = a.n_row_blocks - 1;
@@ -933,6 +939,16 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
     gcount = sg.pos0 + sg.n_pos - tree0;
     ridx += sg.row_off;
   }
+  if constexpr (CAND) {
+    if (loss_listed) {
+      const int n_live = a.fold_cnt[0], g_list = a.fold_cnt[1], n_live_groups = a.fold_cnt[2];  // (g_list <= G)
+      if (int(blockIdx.x) >= n_live_groups * a.n_row_blocks) return;  // (uniform: before any barrier)
+      tg = int(blockIdx.x) % n_live_groups;
+      rb = int(blockIdx.x) / n_live_groups;
+      tree0 = tg * g_list;
+      gcount = n_live - tree0 < g_list ? n_live - tree0 : g_list;
+    }
+  }
   if (gcount > G) gcount = G;
   const bool weighted = a.w != nullptr;
   const uint32_t thr = SrBits<T>::mag(a.tbig);
@@ -947,6 +963,9 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   int my_pos = tree0 + wave + SR_WAVES * lane;
   if (MODE == SR_MODE_FOLD) {  // (the compacted launch: the listed launch position)
     if (listed) my_pos = lane < S ? a.fold_list[size_t(rb) * size_t(a.n_trees) + size_t(my_pos)] : 0;
+  }
+  if constexpr (CAND) {  // (the listed loss launch: the launch's one list)
+    if (loss_listed) my_pos = lane < S ? a.fold_list[my_pos] : 0;
   }
   uint32_t my_pb = 0u, my_pe = 0u;
   uint32_t my_t = 0u;  // PARAM: the caller's index of lane j's tree (its rows of the parameter table)
@@ -974,9 +993,17 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   const uint4* lcode = reinterpret_cast<const uint4*>(sr_smem + plan.code);
   // (a compacted FOLD workgroup's programs are no span: its windows stream from global memory)
   bool lds_code = false;
+  // (a listed loss workgroup's are the span from its first listed program's start to its last one's end, the
+  //  excluded positions' programs between them included: cached when that fits, as when nothing is dead)
   if ((MODE == SR_MODE_LOSS || MODE == SR_MODE_FOLD) && a.code_lds > 0 && a.ends != nullptr && gcount > 0 && !listed) {
-    const uint32_t t_first = a.perm ? a.perm[tree0] : uint32_t(tree0);
-    const uint32_t t_last = a.perm ? a.perm[tree0 + gcount - 1] : uint32_t(tree0 + gcount - 1);
+    uint32_t t_first = a.perm ? a.perm[tree0] : uint32_t(tree0);
+    uint32_t t_last = a.perm ? a.perm[tree0 + gcount - 1] : uint32_t(tree0 + gcount - 1);
+    if constexpr (CAND) {
+      if (loss_listed) {
+        t_first = a.perm[a.fold_list[tree0]];
+        t_last = a.perm[a.fold_list[tree0 + gcount - 1]];
+      }
+    }
     const uint32_t gbase = __builtin_amdgcn_readfirstlane(a.offsets[t_first]);
     const uint32_t gend = __builtin_amdgcn_readfirstlane(a.ends[t_last]);
     if (gend >= gbase && gend - gbase <= uint32_t(a.code_lds)) {
@@ -1410,7 +1437,14 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
             }
             // (small calls under the in-order fold: every live tree's losses, the fold's tables are
             //  composed from them; a tree found dead later leaves garbage the fold never reads)
-            if (a.fold_loss) L::store(a.fold_loss + size_t(tree0 + g) * size_t(a.fold_pos_stride) + size_t(row0) + lane * C, l);
+            if constexpr (CAND) {  // ([position][rows]: a listed launch's position from the list)
+              if (a.fold_loss)
+                L::store(a.fold_loss + size_t(loss_listed ? __builtin_amdgcn_readlane(my_pos, j) : tree0 + g) * size_t(a.fold_pos_stride) +
+                             size_t(row0) + lane * C,
+                         l);
+            } else {
+              if (a.fold_loss) L::store(a.fold_loss + size_t(tree0 + g) * size_t(a.fold_pos_stride) + size_t(row0) + lane * C, l);
+            }
             // (CAND: the losses whole until the candidates are composed; the reduction below overwrites l)
             T lc[CAND ? R : 1];
             if constexpr (CAND) {
@@ -1506,8 +1540,15 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
           }
           if (dead) {
             dmask |= bit;
-            if (use_hint && lane == 0)
-              __hip_atomic_fetch_max(a.hint + tree0 + g, a.hint_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (CAND) {
+              // (a listed launch: tree0 + g is the tree's place in the list; its position is lane j's my_pos)
+              const int hpos = loss_listed ? __builtin_amdgcn_readlane(my_pos, j) : tree0 + g;
+              if (use_hint && lane == 0)
+                __hip_atomic_fetch_max(a.hint + hpos, a.hint_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+              if (use_hint && lane == 0)
+                __hip_atomic_fetch_max(a.hint + tree0 + g, a.hint_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
           }
         } else if (MODE == SR_MODE_FOLD) {
           // the same losses as the LOSS epilogue (rows past the view: 0, which the fold skips)

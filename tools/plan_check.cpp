@@ -331,6 +331,13 @@ void check_fold() {
       CHECK(end <= sr_fold_wg_words(n_rb));
     }
   }
+  {  // the listed loss launch's buffer: the list, word-aligned counters per chunk, the marks, none overlapping
+    for (int64_t nt : {1, 7, 600, 10000, 100000}) {
+      CHECK(sr_loss_list_cnt_off(nt) >= size_t(nt) * sizeof(int32_t) && sr_loss_list_cnt_off(nt) % sizeof(int32_t) == 0);
+      CHECK(sr_loss_list_excl_off(nt) >= sr_loss_list_cnt_off(nt) + size_t(kMaxChunks) * kLossListCnt * sizeof(int32_t));
+      CHECK(sr_loss_list_bytes(nt) >= sr_loss_list_excl_off(nt) + size_t(nt));
+    }
+  }
   {  // 100 trees x 1,000 rows: two row blocks of 512, 400 KiB of losses: stored
     FoldPlanIn in = fold_in(4, 100, 1000, 1000, 1000, 8, 0);
     fold_grids(&in);
