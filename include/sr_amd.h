@@ -528,7 +528,12 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * "fold_cand_est_min" of them have, 4 by default; 0: from the block's first tile alone; `taken` and `rerun`
  * of sr_last_fold_cand then vary from run to run, their sum and every result do not), "fold_compact" (1, the
  * default: the FOLD pass of a plain path-2 call runs over per-row-block lists of the positions left to it;
- * 0: over the loss launch's grid), "loss_compact" (1, the default: the candidate-composing loss launch of such
+ * 0: over the loss launch's grid), "fold_list_wgs" (2048, the default: the live workgroups such a launch
+ * aims for — its lists' entries per workgroup are the fewest, a multiple of the 4 waves, that keep it within
+ * that many workgroups and within its grid; 0: the launch's trees per workgroup; sr_last_phase_ms
+ * out[19 + 4 r ..] report launch r's live workgroups, listed entries, entries per workgroup and longest list),
+ * "trees_per_block" (0, the default: every grid's trees per workgroup by the heuristic; 1..256: that many),
+ * "loss_compact" (1, the default: the candidate-composing loss launch of such
  * a call runs over the launch positions its chunk's dead-tree probe left alive, G per workgroup, and the reduce
  * writes the others' result — non-finite — without reading a partial; 0: over every position),
  * "loss_list_groups" (0, the default: that list is dealt over all of the launch's tree groups; n: over at most n),

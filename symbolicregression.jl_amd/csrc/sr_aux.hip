@@ -749,16 +749,46 @@ __global__ void __launch_bounds__(256) sr_fold_compact_kernel(const int32_t* __r
   }
   if (tid == 0) cnt[blockIdx.x] = base;
 }
-// ... and each row block's first workgroup, G entries per workgroup: wg0[rb] = the exclusive scan of
-// ceil(cnt / G), wg0[n_rb] the launch's live workgroups (one workgroup).
+// ... and each row block's first workgroup, g entries per workgroup: wg0[rb] = the exclusive scan of
+// ceil(cnt / g), wg0[n_rb] the launch's live workgroups, wg0[n_rb + 1] = g (one workgroup).
+// g (sr_plan.h, sr_fold_list_g: the same rule on the host): G when target_wgs is 0 — the launch's trees per
+// workgroup, which leaves a launch whose row blocks list ~100 positions with one workgroup per row block, each
+// wave running its ~27 trees one after another on half the GPU's wave slots; else the smallest multiple of the
+// 4 waves whose workgroups, the sum over the row blocks of ceil(cnt / g), stay within target_wgs and within the
+// launch's grid (the region's, an upper bound), G when none does.  The sum does not grow with g, so the
+// smallest is found by bisection, the whole workgroup summing each candidate.
+__device__ __forceinline__ int sr_fold_list_wgs_sum(const int32_t* __restrict__ cnt, int n_rb, int g, int* s_w) {
+  const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  int v = 0;
+  for (int r = tid; r < n_rb; r += 256) v += (cnt[r] + g - 1) / g;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  if (lane == 0) s_w[wave] = v;
+  __syncthreads();
+  const int total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  __syncthreads();
+  return total;  // (uniform; at most n_rb x np / g + n_rb: below 2^31 for every grid a launch can have)
+}
 __global__ void __launch_bounds__(256) sr_fold_compact_scan_kernel(const int32_t* __restrict__ cnt, int n_rb, int G,
+                                                                   int target_wgs, int grid_wgs,
                                                                    int32_t* __restrict__ wg0) {
   __shared__ int s_w[4];
   const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  int g = G;
+  if (target_wgs > 0 && G >= 4) {
+    const int lim = target_wgs < grid_wgs ? target_wgs : grid_wgs;
+    int lo = 1, hi = G / 4 + 1;  // (candidates 4 lo .. 4 (hi - 1); hi: none fits)
+    while (lo < hi) {            // (uniform)
+      const int mid = (lo + hi) >> 1;
+      if (sr_fold_list_wgs_sum(cnt, n_rb, 4 * mid, s_w) <= lim) hi = mid;
+      else lo = mid + 1;
+    }
+    if (lo <= G / 4) g = 4 * lo;
+  }
   int base = 0;
   for (int r0 = 0; r0 < n_rb; r0 += 256) {
     const int r = r0 + tid;
-    const int v = r < n_rb ? (cnt[r] + G - 1) / G : 0;
+    const int v = r < n_rb ? (cnt[r] + g - 1) / g : 0;
     int inc = v;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -778,13 +808,16 @@ __global__ void __launch_bounds__(256) sr_fold_compact_scan_kernel(const int32_t
     base += total;
     __syncthreads();
   }
-  if (tid == 0) wg0[n_rb] = base;
+  if (tid == 0) {
+    wg0[n_rb] = base;
+    wg0[n_rb + 1] = g;
+  }
 }
-hipError_t sr_launch_fold_compact(const SrFoldTabs& ft, int np, int n_rb, int G, int32_t* list, int32_t* cnt,
-                                  int32_t* wg0, hipStream_t s) {
-  if (np <= 0 || n_rb <= 0 || G <= 0) return hipErrorInvalidValue;
+hipError_t sr_launch_fold_compact(const SrFoldTabs& ft, int np, int n_rb, int G, int target_wgs, int grid_wgs,
+                                  int32_t* list, int32_t* cnt, int32_t* wg0, hipStream_t s) {
+  if (np <= 0 || n_rb <= 0 || G <= 0 || target_wgs < 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sr_fold_compact_kernel, dim3(unsigned(n_rb)), dim3(256), 0, s, ft.code, ft.sq, np, list, cnt);
-  hipLaunchKernelGGL(sr_fold_compact_scan_kernel, dim3(1), dim3(256), 0, s, cnt, n_rb, G, wg0);
+  hipLaunchKernelGGL(sr_fold_compact_scan_kernel, dim3(1), dim3(256), 0, s, cnt, n_rb, G, target_wgs, grid_wgs, wg0);
   return hipGetLastError();
 }
 

@@ -348,7 +348,20 @@ struct sr_ctx {
   // launch's (row block, tree group) grid (0).  Gathered, parametric and row-sharded calls keep the grid.
   int fold_compact = 1;
   DevBuf fold_list;          // [row block][position] int32, laid out as the partials
-  DevBuf fold_wg;            // per region (2 per chunk): {cnt [n_rb], wg0 [n_rb + 1]}
+  DevBuf fold_wg;            // per region (2 per chunk): {cnt [n_rb], wg0 [n_rb + 1], g}
+  // SR_AMD_FOLD_LIST_WGS / "fold_list_wgs": the live workgroups a compacted FOLD launch aims for.  Its list's
+  // entries per workgroup g is chosen on the device from the row blocks' counts (sr_fold_compact_scan_kernel,
+  // sr_plan.h's sr_fold_list_g): the smallest multiple of the 4 waves that keeps the launch within this many
+  // workgroups and within its grid.  0: g = G, the launch's trees per workgroup — C2's row blocks list ~100
+  // positions each, so one workgroup per row block, ~27 trees a wave in turn on half the GPU's wave slots.
+  // Smaller g: more workgroups stage a row block's tiles for fewer trees each.
+  int64_t fold_list_wgs = 2048;
+  // the last call's compacted FOLD launches: per region its row blocks (0: none) and the call's row blocks per
+  // position, for sr_last_phase_ms out[19..] (read back once on request)
+  int fold_wg_nrb[2 * kMaxChunks] = {};
+  int64_t fold_wg_stride_rb = 0;
+  bool fold_wg_read = true;
+  double fold_wg_info[2 * kMaxChunks][4] = {};  // {live workgroups, listed entries, g, the longest list}
   // SR_AMD_LOSS_COMPACT / "loss_compact": the candidate-composing loss launch of such a call runs over the
   // launch positions its chunk's dead-tree probe left alive, less the statically incomplete trees
   // (sr_loss_compact_kernel: one list per launch, dealt over the launch's tree groups, the live workgroups
@@ -617,7 +630,13 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
     int32_t* cnt = ctx->fold_wg.as<int32_t>() + sr_fold_wg_off(fr.idx, job.n_rb);
     int32_t* wg0 = cnt + job.n_rb;
     int32_t* list = ctx->fold_list.as<int32_t>() + fr.off(job.n_rb);
-    SR_HIP_CHECK(sr_launch_fold_compact(ft, np, nrb, fr.a.trees_per_block, list, cnt, wg0, cs));
+    SR_HIP_CHECK(sr_launch_fold_compact(ft, np, nrb, fr.a.trees_per_block, int(ctx->fold_list_wgs),
+                                        int(std::min<int64_t>(fr.n_blocks, kFoldListWgsMax)), list, cnt, wg0, cs));
+    if (!ctx->internal_pass) {  // (sr_last_phase_ms out[19..])
+      ctx->fold_wg_nrb[fr.idx] = nrb;
+      ctx->fold_wg_stride_rb = job.n_rb;
+      ctx->fold_wg_read = false;
+    }
     fa.fold_list = list;
     fa.fold_cnt = cnt;
     fa.fold_wg0 = wg0;
@@ -963,6 +982,11 @@ struct BatchCall {
       ctx->loss_list_nt_last = nt;
       ctx->loss_list_read = true;
       ctx->n_loss_listed_launches_last = ctx->n_loss_live_last = ctx->n_loss_excl_last = 0;
+      for (int r = 0; r < 2 * kMaxChunks; ++r) {
+        ctx->fold_wg_nrb[r] = 0;
+        for (int k = 0; k < 4; ++k) ctx->fold_wg_info[r][k] = 0.0;
+      }
+      ctx->fold_wg_read = true;
       ctx->fold_path_last = fold.path;
       ctx->fold_timed_last = false;
       ctx->fold_cand_read = fold.path != 2;
@@ -3945,6 +3969,8 @@ int sr_init(int device, sr_ctx** out) {
   if (const char* v = std::getenv("SR_AMD_FOLD_PRE_START")) ctx->fold_pre_start = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_SINGLE_PASS")) ctx->fold_single_pass = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_FOLD_COMPACT")) ctx->fold_compact = std::atoi(v) != 0 ? 1 : 0;
+  if (const char* v = std::getenv("SR_AMD_FOLD_LIST_WGS"))
+    ctx->fold_list_wgs = std::max<int64_t>(0, std::min<int64_t>(std::atoll(v), kFoldListWgsMax));
   if (const char* v = std::getenv("SR_AMD_LOSS_COMPACT")) ctx->loss_compact = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("SR_AMD_LOSS_LIST_GROUPS")) ctx->loss_list_groups = std::max(0, std::atoi(v));
   if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST")) ctx->fold_cand_est = std::atoi(v) != 0 ? 1 : 0;
@@ -4735,6 +4761,34 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n) {
   if (n > 16) out[16] = double(ctx->n_loss_listed_launches_last);
   if (n > 17) out[17] = double(ctx->n_loss_live_last);
   if (n > 18) out[18] = double(ctx->n_loss_excl_last);
+  // the last call's compacted FOLD launches, region r (sr_fold_region: 2 chunk, + 1 for the LDS-stack launch) at
+  // out[19 + 4 r ..]: {live workgroups, listed entries, entries per workgroup g, the longest row block's list};
+  // zeros for a region without such a launch
+  if (n > 19 && !ctx->fold_wg_read) {
+    SR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->stream2) SR_HIP_CHECK(hipStreamSynchronize(ctx->stream2));
+    std::vector<int32_t> h(sr_fold_wg_words(ctx->fold_wg_stride_rb));
+    SR_HIP_CHECK(hipMemcpy(h.data(), ctx->fold_wg.p, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int r = 0; r < 2 * kMaxChunks; ++r) {
+      const int nrb = ctx->fold_wg_nrb[r];
+      if (nrb <= 0) continue;
+      const int32_t* cnt = h.data() + sr_fold_wg_off(r, ctx->fold_wg_stride_rb);
+      const int32_t* wg0 = cnt + ctx->fold_wg_stride_rb;
+      int64_t entries = 0, longest = 0;
+      for (int b = 0; b < nrb; ++b) {
+        entries += cnt[b];
+        longest = std::max<int64_t>(longest, cnt[b]);
+      }
+      ctx->fold_wg_info[r][0] = double(wg0[nrb]);
+      ctx->fold_wg_info[r][1] = double(entries);
+      ctx->fold_wg_info[r][2] = double(wg0[nrb + 1]);
+      ctx->fold_wg_info[r][3] = double(longest);
+    }
+    ctx->fold_wg_read = true;
+  }
+  for (int r = 0; r < 2 * kMaxChunks; ++r)
+    for (int k = 0; k < 4; ++k)
+      if (n > 19 + 4 * r + k) out[19 + 4 * r + k] = ctx->fold_wg_info[r][k];
   return SR_OK;
 }
 
@@ -4805,6 +4859,15 @@ int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value) {
   }
   if (std::strcmp(name, "fold_compact") == 0) {  // the FOLD pass over per-row-block work lists (SR_AMD_FOLD_COMPACT)
     ctx->fold_compact = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "trees_per_block") == 0) {  // every grid's trees per workgroup, 0 = heuristic (SR_AMD_TREES_PER_BLOCK)
+    if (value < 0 || value > 256) return set_error(SR_ERR_INVALID_ARG, "trees_per_block: 0, or 1..256 (4 waves of 64 slots)");
+    ctx->tree_group = int(value);
+    return SR_OK;
+  }
+  if (std::strcmp(name, "fold_list_wgs") == 0) {  // the live workgroups a compacted FOLD launch aims for (SR_AMD_FOLD_LIST_WGS)
+    ctx->fold_list_wgs = std::max<int64_t>(0, std::min<int64_t>(value, kFoldListWgsMax));
     return SR_OK;
   }
   if (std::strcmp(name, "loss_compact") == 0) {  // the loss launch over the positions the probe left alive (SR_AMD_LOSS_COMPACT)

@@ -164,8 +164,9 @@ struct SrEvalArgs {
   int4* fold_cand;
   // FOLD, the compacted launch (NULL: workgroup = (row block, tree group) as in the loss launch): per row
   // block rb the launch positions the FOLD pass must run, in launch order, fold_list[rb * n_trees + k],
-  // k < fold_cnt[rb]; workgroups fold_wg0[rb] .. fold_wg0[rb + 1] - 1 take G of them each
-  // (fold_wg0[n_row_blocks]: the total; workgroups past it return at once).  sr_fold_compact_kernel.
+  // k < fold_cnt[rb]; workgroups fold_wg0[rb] .. fold_wg0[rb + 1] - 1 take g <= G of them each
+  // (fold_wg0[n_row_blocks]: the total; workgroups past it return at once; fold_wg0[n_row_blocks + 1]: g,
+  // chosen on the device from the counts).  sr_fold_compact_kernel, sr_fold_compact_scan_kernel.
   // LOSS, the SR_TIER_CAND build's listed launch (NULL: every position): ONE list for the launch, the
   // positions the dead-tree probe left alive (statically incomplete trees left out too), in launch order, fold_list[k], k < fold_cnt[0]; workgroup b
   // takes entries [tg g, tg g + g) of row block rb, g = fold_cnt[1] <= G, tg = b % fold_cnt[2], rb = b / that,
@@ -342,9 +343,11 @@ hipError_t sr_launch_fold_plan(const double* part, int np, int n_rb, const uint3
                                double delta, SrFoldTabs ft, int* slot_next, int slot_cap, const int4* cand,
                                hipStream_t s);
 // The compacted FOLD launch's lists from a region's plan (SrEvalArgs::fold_list / fold_cnt / fold_wg0; G:
-// the launch's trees per workgroup): list [n_rb][np], cnt [n_rb], wg0 [n_rb + 1].
-hipError_t sr_launch_fold_compact(const SrFoldTabs& ft, int np, int n_rb, int G, int32_t* list, int32_t* cnt,
-                                  int32_t* wg0, hipStream_t s);
+// the launch's trees per workgroup): list [n_rb][np], cnt [n_rb], wg0 [n_rb + 2].  target_wgs > 0: the list's
+// entries per workgroup g is the smallest that keeps the launch within target_wgs live workgroups and within
+// grid_wgs, the launch's grid (sr_plan.h, sr_fold_list_g); 0: g = G.
+hipError_t sr_launch_fold_compact(const SrFoldTabs& ft, int np, int n_rb, int G, int target_wgs, int grid_wgs,
+                                  int32_t* list, int32_t* cnt, int32_t* wg0, hipStream_t s);
 template <typename T>
 hipError_t sr_launch_fold_stab(const double* part, int np, int n_rb, int64_t rb_rows, int64_t n, const uint32_t* perm,
                                const SrFoldWho& who, double delta, const T* losses, SrFoldTabs ft,

@@ -462,11 +462,30 @@ inline FoldPlan sr_fold_plan(const FoldPlanIn& in) {
   return out;
 }
 // The compacted FOLD launch (sr_ctx::fold_compact): a call has at most two launches per chunk (register
-// stack, LDS stack), each with its own counters {cnt [n_rb] | wg0 [n_rb + 1]}; region r's start, in words,
+// stack, LDS stack), each with its own counters {cnt [n_rb] | wg0 [n_rb + 1] | g}; region r's start, in words,
 // for a call of n_rb row blocks per position, and the call's words.
 inline int sr_fold_region(int chunk, bool vstk) { return 2 * chunk + (vstk ? 0 : 1); }
 inline size_t sr_fold_wg_off(int region, int64_t n_rb) { return size_t(region) * (2 * size_t(n_rb) + 2); }
 inline size_t sr_fold_wg_words(int64_t n_rb) { return sr_fold_wg_off(2 * kMaxChunks, n_rb); }
+// The entries per workgroup g of a compacted FOLD launch (sr_ctx::fold_list_wgs), from its row blocks' counts:
+// the live workgroups are the sum of ceil(cnt[rb] / g).  target 0: G, the launch's trees per workgroup.  Else
+// the smallest multiple of the 4 waves, at least 4 and at most G, whose workgroups stay within the target and
+// within the launch's grid; G when none does (the grid is the region's groups x row blocks: G always fits it).
+// The host's statement of sr_fold_compact_scan_kernel's rule, which finds the same g by bisection (the sum
+// does not grow with g); region r keeps g in the word after its wg0 [n_rb + 1].
+inline int64_t sr_fold_list_wgs(const int32_t* cnt, int n_rb, int g) {
+  int64_t s = 0;
+  for (int r = 0; r < n_rb; ++r) s += (int64_t(cnt[r]) + g - 1) / g;
+  return s;
+}
+inline int sr_fold_list_g(const int32_t* cnt, int n_rb, int G, int64_t target, int64_t grid) {
+  if (target <= 0 || G < 4) return G;
+  const int64_t lim = std::min(target, grid);
+  for (int g = 4; g <= G; g += 4)
+    if (sr_fold_list_wgs(cnt, n_rb, g) <= lim) return g;
+  return G;
+}
+constexpr int64_t kFoldListWgsMax = int64_t(1) << 24;  // (the knob's bound: past any grid's workgroups)
 // The listed loss launch (sr_ctx::loss_compact): one buffer for the call, {list int32 [nt] | cnt int32
 // [kMaxChunks][kLossListCnt] | excl uint8 [nt]} — a chunk's register-stack region (its only listed launch)
 // uses the slices at its first launch position and the counters of its chunk {listed, entries per workgroup,

@@ -896,7 +896,7 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
   // tree group fastest: the blocks resident at one time share few row blocks (X stays in L2)
   int tg, rb, tree0, gcount;
   const int64_t* ridx = a.row_idx;  // GATHER: this block's row view
-  // FOLD, the compacted launch: the workgroup's row block and its G entries of that block's list (tree0:
+  // FOLD, the compacted launch: the workgroup's row block and its g entries of that block's list (tree0:
   // the first one's index in the list, not a launch position)
   // LOSS, the candidate build's listed launch (sr_loss_compact_kernel): ONE list for the launch, the positions
   // the dead-tree probe left alive, in launch order (fold_cnt[0] of them); workgroup = (row block, fold_cnt[1]
@@ -915,8 +915,11 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
     }
     rb = lo;
     tg = int(blockIdx.x) - a.fold_wg0[rb];
-    tree0 = tg * G;
+    // (the list's entries per workgroup: the scan's choice from the counts, 4 <= g <= G or G itself)
+    const int g_list = a.fold_wg0[a.n_row_blocks + 1];
+    tree0 = tg * g_list;
     gcount = a.fold_cnt[rb] - tree0;
+    gcount = gcount < g_list ? gcount : g_list;
   } else if (a.segs == nullptr) {
     tg = int(blockIdx.x) % a.n_groups;
     rb = int(blockIdx.x) / a.n_groups;

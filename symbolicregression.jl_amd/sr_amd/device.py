@@ -71,7 +71,9 @@ class DeviceContext:
         loss launch of a FOLD-mode call composes the fold's steps under candidate binades: 1 default),
         "fold_cand_est" / "fold_cand_est_min" (those binades guessed from the tree's running prefix: 1 default,
         from 4 finished row blocks on), "fold_compact" (the FOLD pass runs over per-row-block work lists: 1
-        default), "loss_compact" (the loss launch of such a call runs over the launch positions the dead-tree probe
+        default; "fold_list_wgs": the live workgroups that launch aims for, 2048 default, 0 = as many entries per
+        workgroup as the launch has trees; "trees_per_block": every grid's trees per workgroup, 0 = heuristic),
+        "loss_compact" (the loss launch of such a call runs over the launch positions the dead-tree probe
         left alive: 1 default; "loss_list_groups": over at most that many tree groups, 0 default: the launch's),
         "tail_chunk" (such a call with the candidate launch runs three chunks, the last one value/12
         of the trees, whose last two fold chains run side by side: 4 default, 0 the two-chunk pipeline),

@@ -6,7 +6,9 @@ Every argument is one configuration (knob=value pairs joined by commas; the knob
 library's defaults).  The configurations are alternated over --rounds rounds of --steps timed steps each; per
 configuration and round the median step_ms, and once per configuration the (tree, row block) pairs the plan
 took from the loss launch's candidates / left to the FOLD pass (sr_last_fold_cand) and the listed loss
-launches' positions (sr_last_phase_ms out[16..18])."""
+launches' positions (sr_last_phase_ms out[16..18]), and per compacted FOLD launch (region 2 chunk, + 1 for
+the LDS-stack launch) its live workgroups, listed entries, entries per workgroup g and longest row block's list
+(out[19 + 4 region ..])."""
 import argparse
 import ctypes
 import os
@@ -22,7 +24,7 @@ from bench import C2_OPS, c2_data, single_gpu_call
 from sr_amd import Dataset, Options, _lib, flatten_trees, gen_random_population
 
 DEFAULTS = dict(loss_compact=1, loss_list_groups=0, tail_chunk=4, first_chunk=6, fold_compact=1, fold_cand_est=1, exact_early=1,
-                code_cache=1, probe=2)
+                code_cache=1, probe=2, fold_list_wgs=2048)
 
 
 def main():
@@ -55,10 +57,12 @@ def main():
                 ts.append((time.perf_counter() - t) * 1e3)
             med[i].append(float(np.median(ts)))
             if info[i] is None:
-                out = (ctypes.c_double * 19)()
-                _lib.check(_lib.lib.sr_last_phase_ms(ctx.handle, out, 19))
+                out = (ctypes.c_double * 51)()
+                _lib.check(_lib.lib.sr_last_phase_ms(ctx.handle, out, 51))
                 info[i] = dict(ctx.last_fold_cand(), listed_launches=int(out[16]), listed=int(out[17]),
-                               excluded=int(out[18]), kernel_ms=round(ctx.last_kernel_ms()[0], 3))
+                               excluded=int(out[18]), kernel_ms=round(ctx.last_kernel_ms()[0], 3),
+                               fold_lists=[(r, int(out[19 + 4 * r]), int(out[20 + 4 * r]), int(out[21 + 4 * r]),
+                                            int(out[22 + 4 * r])) for r in range(8) if out[21 + 4 * r] > 0])
     for k, v in DEFAULTS.items():
         ctx.set_tuning(k, v)
     for cfg, m, inf in zip(a.configs, med, info):

@@ -399,12 +399,70 @@ void check_fold() {
   CHECK(sr_max_shard_rows({}, 7) == 7 && sr_max_shard_rows({0, 5, 30, 31}, 5) == 25 && sr_max_shard_rows({0, 5}, 9) == 9);
 }
 
+// The compacted FOLD launch's entries per workgroup (sr_fold_list_g): the rule's bounds and its minimality,
+// and the bisection sr_fold_compact_scan_kernel runs instead of the scan over g (the same g: the workgroup sum
+// does not grow with g).
+int bisect_g(const std::vector<int32_t>& cnt, int G, int64_t target, int64_t grid) {
+  int g = G;
+  if (target > 0 && G >= 4) {
+    const int64_t lim = std::min(target, grid);
+    int lo = 1, hi = G / 4 + 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (sr_fold_list_wgs(cnt.data(), int(cnt.size()), 4 * mid) <= lim) hi = mid;
+      else lo = mid + 1;
+    }
+    if (lo <= G / 4) g = 4 * lo;
+  }
+  return g;
+}
+void check_fold_list(Rng& rng) {
+  {  // C2's last chunk as the issue reasons it: 512 row blocks of ~105 entries, row block 0 lists all 1,170
+    std::vector<int32_t> cnt(512, 105);
+    cnt[0] = 1170;
+    const int64_t grid = 512 * 27;
+    CHECK(sr_fold_list_g(cnt.data(), 512, 128, 0, grid) == 128);
+    CHECK(sr_fold_list_wgs(cnt.data(), 512, 128) == 511 + 10);
+    CHECK(sr_fold_list_g(cnt.data(), 512, 128, 1024, grid) == 108);  // (two per row block: 511 x 2 + 21 = 1,043 at 56)
+    CHECK(sr_fold_list_g(cnt.data(), 512, 128, 2048, grid) == 36);   // 511 x 3 + 33
+    CHECK(sr_fold_list_g(cnt.data(), 512, 128, 1 << 20, grid) == 8);  // (4 would need 14,090 workgroups)
+    CHECK(sr_fold_list_g(cnt.data(), 512, 128, 1 << 20, 1 << 20) == 4);
+    CHECK(sr_fold_list_g(cnt.data(), 512, 128, 100, grid) == 128);  // no g meets the target: G
+  }
+  for (int it = 0; it < 2000; ++it) {
+    const int n_rb = 1 + rng.below(40);
+    const int G = std::vector<int>{1, 3, 4, 5, 8, 9, 16, 32, 64, 128, 256}[size_t(rng.below(11))];
+    const int np = 1 + rng.below(3000);
+    std::vector<int32_t> cnt(size_t(n_rb), 0);
+    const int kind = rng.below(4);
+    for (int r = 0; r < n_rb; ++r)
+      cnt[size_t(r)] = kind == 0 ? 0 : (kind == 1 ? np : (r == 0 ? np : rng.below(np + 1) / (1 + rng.below(12))));
+    const int64_t grid = int64_t(n_rb) * ((np + G - 1) / G);
+    const int64_t target = std::vector<int64_t>{0, 1, 7, 100, 1000, 5000, kFoldListWgsMax}[size_t(rng.below(7))];
+    const int g = sr_fold_list_g(cnt.data(), n_rb, G, target, grid);
+    CHECK(g == bisect_g(cnt, G, target, grid));
+    CHECK(g == G || (G >= 4 && target > 0 && g % 4 == 0 && g >= 4 && g < G));
+    CHECK(sr_fold_list_wgs(cnt.data(), n_rb, g) <= grid);  // the launch always fits its grid
+    if (target == 0) CHECK(g == G);
+    if (g != G) {
+      CHECK(sr_fold_list_wgs(cnt.data(), n_rb, g) <= target);
+      if (g > 4) CHECK(sr_fold_list_wgs(cnt.data(), n_rb, g - 4) > std::min(target, grid));  // the smallest
+    }
+    // every listed entry belongs to exactly one workgroup's [k g, k g + g) of its row block
+    for (int r = 0; r < n_rb; ++r) {
+      const int64_t w = (int64_t(cnt[size_t(r)]) + g - 1) / g;
+      CHECK(w * g >= cnt[size_t(r)] && (w == 0 || (w - 1) * g < cnt[size_t(r)]));
+    }
+  }
+}
+
 }  // namespace
 
 int main() {
   check_grids();
   check_chunks();
   Rng rng{12345};
+  check_fold_list(rng);
   for (int64_t nc : {1, 2, 127, 128, 129, 1000})
     for (int tree_group : {0, 4, 32}) check_order(rng, nc, tree_group);
   check_fold();
