@@ -327,6 +327,25 @@ int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, co
                              int loss_kind, void* out_loss, void* out_grad, uint8_t* out_complete);
 
 /*
+ * The same for ParametricExpression trees (sr_param_batch; the dataset uploaded with classes).  Tree t's
+ * gradient is DynamicExpressions' get_scalar_constants(::ParametricExpression) order:
+ *   [ its nc_t constants in pre-order | max_parameters x n_classes parameter entries, column-major:
+ *     entry (k-1) + max_parameters (c-1) for parameter k of class c ]
+ * (the parameter part has the per-tree layout of sr_param_batch.parameters), and out_grad holds
+ * sum_t (nc_t + max_parameters n_classes) values.  Every parameter entry is present: exactly 0 for a
+ * parameter the tree does not use and for a class with no row among the evaluated rows; all 0 (and the
+ * loss Inf) for an incomplete tree.  The limit of 128 is one on a tree's constants.  SR_ERR_INVALID_ARG for
+ * a dataset without classes or a mismatched n_classes / max_parameters, as the parametric loss calls.
+ */
+int sr_eval_grad_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind,
+                                  void* out_loss, void* out_grad, uint8_t* out_complete);
+int sr_eval_grad_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                        const sr_param_batch* params, const int32_t* tree_view, int n_views,
+                                        const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
+                                        void* out_grad, uint8_t* out_complete);
+
+/*
  * Host-only dry run of the tree compiler (no device needed): compile `trees` for an operator set
  * and report, per tree, the program length in instructions (out_len), whether the tree is
  * incomplete independent of X (out_static_bad), and the operand-stack depth it needs
@@ -476,6 +495,20 @@ int sr_optimize_constants_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id,
                                 const int64_t* row_idx, int64_t n_idx, int loss_kind, int iterations,
                                 int64_t f_calls_limit, int nrestarts, uint64_t seed, void* out_consts, void* out_loss,
                                 uint8_t* out_improved, int64_t* out_f_calls);
+
+/*
+ * The same for ParametricExpression trees: the optimised vector is x = [constants; vec(parameters)]
+ * (nc_t + max_parameters n_classes entries, the layout of sr_eval_grad_batch_parametric), as the reference's
+ * get_scalar_constants hands it to Optim — Newton when it has one entry, nothing to do when it has none.
+ * Restarts perturb the WHOLE vector (one draw per entry, constants first, then the matrix column-major), so
+ * parameters the tree does not use are perturbed too and adopted when that start wins.  out_params:
+ * [n_trees][n_classes][max_parameters] (sr_param_batch.parameters' layout), unchanged where not improved.
+ */
+int sr_optimize_constants_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                           const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx,
+                                           int loss_kind, int iterations, int64_t f_calls_limit, int nrestarts,
+                                           uint64_t seed, void* out_consts, void* out_params, void* out_loss,
+                                           uint8_t* out_improved, int64_t* out_f_calls);
 
 /* The same optimiser with the scoring calls answered by CPU callbacks (sr_loss_fn / sr_grad_fn, as
  * sr_search_use_callbacks): a test seam and the host-port baseline.  dtype = the trees' element type. */

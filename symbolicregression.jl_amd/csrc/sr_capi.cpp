@@ -29,6 +29,7 @@
 #include "sr_eval.h"
 #include "sr_fold.h"
 #include "sr_fold_dev.h"
+#include "sr_param_pack.h"
 
 namespace {
 
@@ -258,6 +259,7 @@ struct sr_ctx {
   int vstk_rows = 0;        // SR_AMD_VSTK_ROWS / "vstk_rows": rows per lane of the register-stack kernel (0: default)
   int grad_rows_force = 0;  // SR_AMD_GRAD_ROWS / "grad_rows": the gradient kernel's rows per lane (0: chosen per call)
   int grad_sort = 1;        // SR_AMD_GRAD_SORT / "grad_sort": gradient work items ordered by program cost
+  int grad_lane_bins = 1;   // "grad_lane_bins": parametric gradients bin small slots x classes per lane (sr_eval.h)
   DevBuf group_cnt;      // its per-group counters (zeroed at allocation; each launch leaves them zero)
   int first_chunk = 6;   // SR_AMD_FIRST_CHUNK: the two-chunk pipeline's first chunk is 1/first_chunk
   int64_t chunk_min = 1024;  // SR_AMD_CHUNK_MIN: the two-chunk pipeline runs when its first chunk holds this many trees
@@ -2844,10 +2846,30 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
   const int64_t n_eval = gather ? n_idx : ds->n;
   const int n_views = (views && gather) ? views->n_views : 1;
   auto view_of = [&](int64_t t) -> int { return n_views > 1 ? int(views->tree_view[t]) : 0; };
+  // a parametric call (sr_ctx::param, set by the *_parametric entry points; the loss pass above has
+  // checked the batch against the dataset): the tree's tangents are its constants, then the parameters it
+  // uses (a compact rank: an unused parameter makes no tangent, no window and no work item), and the
+  // gradient of tree t is [its nc constants | K x C parameter entries, column-major] (sr_param_pack.h)
+  const sr_param_batch* const pb = ctx->param;
+  const bool parametric = pb != nullptr;
+  const int64_t pK = parametric ? pb->max_parameters : 0, pC = parametric ? pb->n_classes : 0;
+  const SrParamNodes pnodes{parametric ? pb->is_parameter : nullptr, parametric ? pb->parameter : nullptr,
+                            int32_t(pK)};
   SrProgramBatch<T> prog;
   std::string err;
-  rc = sr_compile_batch<T>(*trees, ops, n_eval, ds->nf, true, &prog, &err);
+  rc = sr_compile_batch<T>(*trees, ops, n_eval, ds->nf, true, &prog, &err, nullptr, parametric ? &pnodes : nullptr);
   if (rc != SR_OK) return set_error(rc, err);
+  std::vector<uint32_t> tan_off(size_t(nt) + 1, 0u), tan_par;
+  if (parametric) {
+    std::vector<uint32_t> used;
+    for (int64_t t = 0; t < nt; ++t) {
+      srpp::used_parameters(pb->is_parameter, pb->parameter, trees->degree, trees->offsets[t], trees->offsets[t + 1], &used);
+      tan_par.insert(tan_par.end(), used.begin(), used.end());
+      tan_off[size_t(t) + 1] = uint32_t(tan_par.size());
+    }
+  }
+  // where tree t's gradient starts in out_grad
+  auto goff = [&](int64_t t) -> size_t { return size_t(prog.const_off[size_t(t)]) + size_t(t) * size_t(pK * pC); };
   // pre-order constants of every tree (get_scalar_constants order)
   const T* vals = static_cast<const T*>(trees->val);
   std::vector<T> consts;
@@ -2856,7 +2878,7 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
     for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i)
       if (trees->degree[i] == 0 && trees->constant[i]) consts.push_back(vals[i]);
   T* g = static_cast<T*>(out_grad);
-  std::fill(g, g + consts.size(), T(0));
+  std::fill(g, g + consts.size() + size_t(nt) * size_t(pK * pC), T(0));
   // work items per tangent width: (tree, first constant)
   // tangent buckets: a tree runs with the narrowest width that holds its constants (1, 2, 4, 8; more
   // than 8: passes of 16), so a one-constant tree carries one tangent, not four
@@ -2864,9 +2886,11 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
   std::vector<uint32_t> items[kNB], k0s[kNB];
   const int kts[kNB] = {1, 2, 4, 8, 16};
   for (int64_t t = 0; t < nt; ++t) {
-    const uint32_t nc = prog.n_consts[size_t(t)];
+    // (tangents: the constants and, in a parametric call, the used parameters behind them; the limit is
+    //  one on constants, which live in the kernel's cval lanes)
+    const uint32_t nc = prog.n_consts[size_t(t)] + (tan_off[size_t(t) + 1] - tan_off[size_t(t)]);
     if (nc == 0 || !out_complete[t]) continue;
-    if (nc > 128) return set_error(SR_ERR_TOO_DEEP, "more than 128 constants in one tree");
+    if (prog.n_consts[size_t(t)] > 128) return set_error(SR_ERR_TOO_DEEP, "more than 128 constants in one tree");
     const int b = nc <= 1 ? 0 : (nc <= 2 ? 1 : (nc <= 4 ? 2 : (nc <= 8 ? 3 : 4)));
     for (uint32_t k0 = 0; k0 < nc; k0 += uint32_t(kts[b])) {
       items[b].push_back(uint32_t(t));
@@ -2949,13 +2973,36 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
   const size_t o_coff = al(o_cons + consts.size() * sizeof(T));
   size_t o_items[kNB], o_vals[kNB], o_segs[kNB];
   size_t at = al(o_coff + prog.const_off.size() * sizeof(uint32_t)), n_vals_all = 0;
+  // parametric: the table [tree][parameter][class] (the loss pass's layout), the tangent lists, and per
+  // bucket every item's first class bin (items in their final order) behind its work items
+  size_t o_ptab = 0, o_toff = 0, o_tpar = 0, o_bins[kNB] = {};
+  std::vector<uint32_t> item_bin[kNB];
+  size_t n_bins[kNB] = {};
+  if (parametric) {
+    o_ptab = at;
+    o_toff = al(o_ptab + size_t(nt) * size_t(pK * pC) * sizeof(T));
+    o_tpar = al(o_toff + tan_off.size() * sizeof(uint32_t));
+    at = al(o_tpar + tan_par.size() * sizeof(uint32_t));
+    for (int b = 0; b < kNB; ++b) {
+      item_bin[b].resize(items[b].size());
+      for (size_t i = 0; i < items[b].size(); ++i) {
+        const uint32_t t = items[b][i], k0 = k0s[b][i], ncs = prog.n_consts[t], nu = tan_off[t + 1] - tan_off[t];
+        const uint32_t q0 = k0 < ncs ? ncs - k0 : 0u, q1 = std::min<uint32_t>(uint32_t(kts[b]), ncs + nu - k0);
+        item_bin[b][i] = uint32_t(n_bins[b]);
+        if (q1 > q0) n_bins[b] += size_t(q1 - q0) * size_t(pC);
+      }
+      if (n_bins[b] > size_t(0x7fffffff)) return set_error(SR_ERR_INVALID_ARG, "too many parameter bins");
+    }
+  }
   for (int b = 0; b < kNB; ++b) {
     o_items[b] = at;
-    at = al(at + 2 * items[b].size() * sizeof(uint32_t));
+    at = al(at + (parametric ? 3 : 2) * items[b].size() * sizeof(uint32_t));
     o_segs[b] = at;
     at = al(at + segs[b].size() * sizeof(SrSegment));
     o_vals[b] = n_vals_all;
     n_vals_all += items[b].size() * size_t(kts[b]);
+    o_bins[b] = n_vals_all;
+    n_vals_all += n_bins[b];
   }
   const size_t stage_bytes = at;
   SR_HIP_CHECK(ctx->g_code.ensure(stage_bytes + 16));
@@ -2969,6 +3016,18 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
     uint32_t* d = reinterpret_cast<uint32_t*>(hs + o_items[b]);
     std::copy(items[b].begin(), items[b].end(), d);
     std::copy(k0s[b].begin(), k0s[b].end(), d + items[b].size());
+    if (parametric) std::copy(item_bin[b].begin(), item_bin[b].end(), d + 2 * items[b].size());
+  }
+  if (parametric) {
+    // (each tree's matrix [class][parameter] transposed, as run_batch's stage_param_table)
+    T* hp = reinterpret_cast<T*>(hs + o_ptab);
+    const T* src = static_cast<const T*>(pb->parameters);
+    const size_t st = size_t(pK * pC);
+    for (int64_t t = 0; t < nt; ++t)
+      for (int64_t c = 0; c < pC; ++c)
+        for (int64_t k = 0; k < pK; ++k) hp[size_t(t) * st + size_t(k * pC + c)] = src[size_t(t) * st + size_t(c * pK + k)];
+    std::memcpy(hs + o_toff, tan_off.data(), tan_off.size() * sizeof(uint32_t));
+    if (!tan_par.empty()) std::memcpy(hs + o_tpar, tan_par.data(), tan_par.size() * sizeof(uint32_t));
   }
   char* ds_ = ctx->g_code.as<char>();
   SR_HIP_CHECK(ctx->g_out.ensure(n_vals_all * sizeof(double) + 16));
@@ -2985,9 +3044,15 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
     // default's tile + stacks would not fit (many features, Float64, deep trees: ADVICE r3)
     int bdepth = 1;
     for (uint32_t t : items[b]) bdepth = std::max(bdepth, int(prog.depth[t]));
-    const int rows = sr_grad_launch_rows(int(sizeof(T)), kt, int(ds->nf), ds->w != nullptr, bdepth, kWaves, kLdsMax,
-                                         ctx->grad_rows_force);
-    if (rows == 0) return set_error(SR_ERR_TOO_DEEP, "gradient tile needs more than 160 KiB of LDS");
+    const int rows = parametric ? sr_grad_param_launch_rows(int(sizeof(T)), kt, int(ds->nf), ds->w != nullptr, bdepth, kWaves,
+                                                            kLdsMax, int(pC),
+                                                            sr_grad_param_lane_slots(int(sizeof(T)), kt, int(pK), int(pC), ctx->grad_lane_bins != 0),
+                                                            ctx->grad_rows_force)
+                                : sr_grad_launch_rows(int(sizeof(T)), kt, int(ds->nf), ds->w != nullptr, bdepth, kWaves, kLdsMax,
+                                                      ctx->grad_rows_force);
+    if (rows == 0)
+      return set_error(SR_ERR_TOO_DEEP, parametric ? "gradient tile and class bins need more than 160 KiB of LDS"
+                                                   : "gradient tile needs more than 160 KiB of LDS");
     int64_t n_groups = (ni + kWaves - 1) / kWaves;
     if (!segs[b].empty()) {  // (view-pure groups: a few more than ni / kWaves)
       n_groups = 0;
@@ -3012,7 +3077,7 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
     }
     if (!segs[b].empty()) std::memcpy(hs + o_segs[b], segs[b].data(), segs[b].size() * sizeof(SrSegment));
     lc[b] = Launch{n_rb, tiles_per_block, n_groups, rows, bdepth};
-    part_need = std::max(part_need, size_t(n_rb) * size_t(ni) * size_t(kt));
+    part_need = std::max(part_need, size_t(n_rb) * (size_t(ni) * size_t(kt) + n_bins[b]));
   }
   SR_HIP_CHECK(hipMemcpyAsync(ds_, hs, stage_bytes, hipMemcpyHostToDevice, s));
   // (buckets run one after another on the stream, so they share the partials buffer)
@@ -3033,6 +3098,7 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
       per_row += 3.0 + kt;
       for (uint32_t i = prog.offsets[t]; i < prog.offsets[t + 1]; ++i) {
         const uint32_t opc = prog.code[i].op & SR_OP_MASK;
+        if (opc == SR_OP_LOAD_PARAM || opc == SR_OP_LOAD_PARAM_PUSH) continue;
         if (opc >= SR_OP_BINARY0) per_row += 3.0 + 2.0 * kt;
         else if (opc >= SR_OP_UNARY0 && opc < SR_OP_LOAD_DERIVED) per_row += 2.0 + kt;
       }
@@ -3070,12 +3136,31 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
       a.n_segs = int(segs[b].size());
     }
     if (ctx->timing) SR_HIP_CHECK(hipEventRecord(ctx->ev_g0[b], s));
-    SR_HIP_CHECK(sr_launch_grad_any<T>(a, kt, gather, lc[b].rows, int(lc[b].n_rb * lc[b].n_groups), s));
+    SrGradParamArgs<T> pa{};
+    if (parametric) {
+      a.nf = int(ds->nf) + 1;  // (the hidden class row is staged too)
+      pa.ptab = reinterpret_cast<const T*>(ds_ + o_ptab);
+      pa.p_stride = int(pK * pC);
+      pa.n_classes = int(pC);
+      pa.tan_off = reinterpret_cast<const uint32_t*>(ds_ + o_toff);
+      pa.tan_par = reinterpret_cast<const uint32_t*>(ds_ + o_tpar);
+      pa.item_bin = a.item_tree + 2 * ni;
+      pa.ppart = a.part + size_t(lc[b].n_rb) * size_t(ni) * size_t(kt);
+      pa.n_bins = int(n_bins[b]);
+      pa.lane_slots = sr_grad_param_lane_slots(int(sizeof(T)), kt, int(pK), int(pC), ctx->grad_lane_bins != 0);
+      const int nblk = int(lc[b].n_rb * lc[b].n_groups);
+      SR_HIP_CHECK(gather ? (sr_launch_grad_param_any<T, true>(a, pa, kt, lc[b].rows, nblk, s))
+                          : (sr_launch_grad_param_any<T, false>(a, pa, kt, lc[b].rows, nblk, s)));
+    } else {
+      SR_HIP_CHECK(sr_launch_grad_any<T>(a, kt, gather, lc[b].rows, int(lc[b].n_rb * lc[b].n_groups), s));
+    }
     if (ctx->timing) {
       SR_HIP_CHECK(hipEventRecord(ctx->ev_g1[b], s));
       ctx->grad_timed[b] = true;
     }
     SR_HIP_CHECK(sr_launch_grad_reduce(a.part, int(lc[b].n_rb), int(size_t(ni) * kt), ctx->g_out.as<double>() + o_vals[b], s));
+    if (parametric)  // (the class bins: row blocks in order, as the constants' partials)
+      SR_HIP_CHECK(sr_launch_grad_reduce(pa.ppart, int(lc[b].n_rb), pa.n_bins, ctx->g_out.as<double>() + o_bins[b], s));
   }
   double* out = ctx->h_grad.as<double>();  // (the staging image is no longer needed: the upload is done)
   SR_HIP_CHECK(hipMemcpyAsync(out, ctx->g_out.p, n_vals_all * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -3086,7 +3171,17 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
       const uint32_t t = items[b][i], k0 = k0s[b][i];
       const uint32_t nc = prog.n_consts[t];
       for (int q = 0; q < kt && k0 + uint32_t(q) < nc; ++q)
-        g[prog.const_off[t] + k0 + uint32_t(q)] = T(out[o_vals[b] + i * size_t(kt) + size_t(q)] / vden[size_t(view_of(t))]);
+        g[goff(t) + k0 + uint32_t(q)] = T(out[o_vals[b] + i * size_t(kt) + size_t(q)] / vden[size_t(view_of(t))]);
+      if (!parametric) continue;
+      // the window's parameter tangents: bin (rank, class) -> entry nc + k + K class
+      const uint32_t nu = tan_off[t + 1] - tan_off[t];
+      const uint32_t q0 = k0 < nc ? nc - k0 : 0u, q1 = std::min<uint32_t>(uint32_t(kt), nc + nu - k0);
+      for (uint32_t q = q0; q < q1; ++q) {
+        const uint32_t k = tan_par[tan_off[t] + (k0 + q - nc)];
+        for (int64_t c = 0; c < pC; ++c)
+          g[goff(t) + nc + size_t(k) + size_t(pK) * size_t(c)] =
+              T(out[o_bins[b] + item_bin[b][i] + size_t(q - q0) * size_t(pC) + size_t(c)] / vden[size_t(view_of(t))]);
+      }
     }
   }
   return SR_OK;
@@ -4282,6 +4377,48 @@ int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, co
                                 out_complete, v);
 }
 
+// Gradients of ParametricExpression trees: per tree [nc constants | K x C parameter entries, column-major]
+// (sr_param_pack.h); the loss and flags are sr_eval_loss_batch(_views)_parametric's.
+int sr_eval_grad_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind,
+                                  void* out_loss, void* out_grad, uint8_t* out_complete) {
+  int rc = validate_common(ctx, ds, opset_id, trees);
+  if (rc != SR_OK) return rc;
+  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
+  if (trees->n_trees > 0 && (!out_loss || !out_grad || !out_complete))
+    return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
+  if (!ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  ParamScope scope(ctx, params);
+  if (ds->dtype == SR_DTYPE_F32)
+    return eval_grad_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_grad, out_complete);
+  return eval_grad_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_grad, out_complete);
+}
+
+int sr_eval_grad_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                        const sr_param_batch* params, const int32_t* tree_view, int n_views,
+                                        const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
+                                        void* out_grad, uint8_t* out_complete) {
+  int rc = validate_common(ctx, ds, opset_id, trees);
+  if (rc != SR_OK) return rc;
+  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
+  if ((rc = check_views(trees, tree_view, n_views, view_rows, view_len)) != SR_OK) return rc;
+  if (trees->n_trees > 0 && (!out_loss || !out_grad || !out_complete))
+    return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
+  if (!ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  ParamScope scope(ctx, params);
+  const ViewSpec vs{tree_view, n_views, view_len};
+  const ViewSpec* v = n_views > 1 ? &vs : nullptr;
+  if (ds->dtype == SR_DTYPE_F32)
+    return eval_grad_impl<float>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_grad,
+                                 out_complete, v);
+  return eval_grad_impl<double>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_grad,
+                                out_complete, v);
+}
+
 int sr_eval_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                        const int64_t* row_idx, int64_t n_idx, void* out_pred, uint8_t* out_complete) {
   int rc = validate_common(ctx, ds, opset_id, trees);
@@ -4798,6 +4935,10 @@ int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value) {
   Lock l(ctx);
   if (std::strcmp(name, "derived") == 0) {
     ctx->derived = value != 0 ? 1 : 0;
+    return SR_OK;
+  }
+  if (std::strcmp(name, "grad_lane_bins") == 0) {  // parametric gradients: per-lane class accumulators where they fit
+    ctx->grad_lane_bins = value != 0 ? 1 : 0;       // (0: the masked wave sums everywhere; the two differ in rounding)
     return SR_OK;
   }
   if (std::strcmp(name, "grad_sort") == 0) {  // gradient work items ordered by program cost (SR_AMD_GRAD_SORT)

@@ -611,9 +611,10 @@ struct TreeCompiler {
     if (err != SR_OK) return;
     if (emit_pair(i, bop)) {
       // both operands in one instruction
-    } else if (effleaf(b) && !(par(b) && effleaf(a) && !par(a))) {  // op(tos = left, operand = right leaf)
+    } else if (effleaf(b) && !(!with_const_index && par(b) && effleaf(a) && !par(a))) {  // op(tos = left, operand = right leaf)
       // (constant op parameter: the parameter's LOAD first, the constant as its operand below — a
-      //  LOAD_CONST is only ever a constant tree's root)
+      //  LOAD_CONST is only ever a constant tree's root.  Not in gradient programs, which keep the plain
+      //  twin's order instruction by instruction: LOAD_CONST, then the P operand)
       emit(a);
       if (fuse_const_operand(i, b, bop, false)) return;
       const_operand_check(b);
@@ -777,10 +778,6 @@ int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_r
   const int64_t nt = trees.n_trees;
   if (pn && nt > 0 && (!pn->is_parameter || !pn->parameter || pn->max_parameters < 0)) {
     *err = "sr_param_batch has NULL arrays";
-    return SR_ERR_INVALID_ARG;
-  }
-  if (pn && with_const_index) {
-    *err = "gradient programs take no parameter leaves";
     return SR_ERR_INVALID_ARG;
   }
   if (nt < 0 || (nt > 0 && (!trees.offsets || !trees.degree || !trees.op || !trees.feature ||

@@ -73,7 +73,9 @@ uint32_t sr_instruction_cost(uint32_t opcode);
 // with_const_index).
 // pn: optional parameter leaves of a ParametricExpression batch (sr_param_batch's per-node arrays, parallel
 // to the tree batch's): such a leaf is a feature leaf to every decision of the compiler and becomes
-// LOAD_PARAM / a P binary operand (sr_ops.h); not with with_const_index.
+// LOAD_PARAM / a P binary operand (sr_ops.h).  With with_const_index (gradient programs) the program is
+// that of the tree with p_k replaced by feature nfeatures + k, apart from those opcodes and the operand
+// index (k - 1): the same length, depth and constant slots (make param-grad-check).
 struct SrParamNodes {
   const uint8_t* is_parameter;
   const uint16_t* parameter;  // 1-based, <= max_parameters

@@ -291,9 +291,14 @@ constexpr int sr_grad_rows_per_lane(int kt) { return kt <= 2 ? 8 : (kt <= 4 ? 4 
 constexpr int sr_grad_tile_rows(int rows) { return 64 * rows > 256 ? 64 * rows : 256; }
 // LDS of one gradient workgroup (W waves): the X / y / w tile and the waves' operand stacks (value +
 // KT tangents per row, stack_depth slots)
-inline size_t sr_grad_lds_bytes(int elem_size, int kt, int rows, int nf, bool weighted, int stack_depth, int waves) {
-  return (size_t(nf) + 1 + (weighted ? 1 : 0)) * size_t(sr_grad_tile_rows(rows)) * size_t(elem_size) +
-         size_t(waves) * size_t(stack_depth) * size_t(1 + kt) * size_t(rows) * 64 * size_t(elem_size);
+// n_classes > 0: a parametric launch — the hidden class row is staged too, and every wave keeps f64 class
+// bins behind the stacks: [kt][n_classes], or with lane_slots > 0 one accumulator per lane,
+// [lane_slots][n_classes][64] (sr_grad_param_lane_slots)
+inline size_t sr_grad_lds_bytes(int elem_size, int kt, int rows, int nf, bool weighted, int stack_depth, int waves,
+                                int n_classes = 0, int lane_slots = 0) {
+  return (size_t(nf) + 1 + (weighted ? 1 : 0) + (n_classes > 0 ? 1 : 0)) * size_t(sr_grad_tile_rows(rows)) * size_t(elem_size) +
+         size_t(waves) * size_t(stack_depth) * size_t(1 + kt) * size_t(rows) * 64 * size_t(elem_size) +
+         size_t(waves) * size_t(lane_slots > 0 ? lane_slots * 64 : kt) * size_t(n_classes > 0 ? n_classes : 0) * sizeof(double);
 }
 // Rows per lane a bucket of KT tangents runs with (results do not depend on it): `force` when it is
 // one the kernels exist for and fits; otherwise the preferred count (Float32: the largest; Float64:
@@ -312,6 +317,53 @@ inline int sr_grad_launch_rows(int elem_size, int kt, int nf, bool weighted, int
   return fits(1, lds_max) ? 1 : 0;
 }
 hipError_t sr_launch_grad_reduce(const double* part, int n_row_blocks, int n_vals, double* out, hipStream_t s);
+// The parametric build of the gradient kernel (sr_grad_param_kernel: ParametricExpression trees).  A tree's
+// tangents are its constants, then the parameters it uses in ascending index (tan_par[tan_off[t] ..
+// tan_off[t + 1])); work items are windows of that list.  A parameter tangent's per-class sums go to
+// ppart[row block][n_bins] at item_bin[item] + (its rank among the window's parameter tangents) x n_classes
+// + class; SrGradArgs::nf counts the staged hidden class row.
+template <typename T>
+struct SrGradParamArgs {
+  const T* ptab;              // [tree][parameter][class], as SrParamArgs
+  int p_stride;
+  int n_classes;
+  const uint32_t* tan_off;    // [n_trees + 1]
+  const uint32_t* tan_par;    // used parameter indices (0-based)
+  const uint32_t* item_bin;   // [n_items]
+  double* ppart;
+  int n_bins;
+  int lane_slots;             // > 0: per-lane class accumulators for that many parameter tangents per window
+};
+// The binning scheme of a parametric launch of kt tangents: 0 = per 64-row group one masked wave sum per
+// class present (any n_classes); s > 0 = per-lane accumulators [s][n_classes][64], s = min(kt,
+// max_parameters) the most parameter tangents a window can hold, taken for Float32 while s x n_classes <= 16
+// (32 KiB of LDS at 4 waves; measured: at 8 classes the Float32 kernels run 19 % shorter with it, the Float64
+// ones 22 % longer — DESIGN.md 13.1 — so Float64 keeps the wave sums).  The two sum in different orders, so which one runs must not depend on the launch: it
+// follows from the element type, the tree's own width, the batch's max_parameters and the dataset's classes alone (and the
+// "grad_lane_bins" knob, which results therefore depend on).
+constexpr int sr_grad_param_lane_slots(int elem_size, int kt, int max_parameters, int n_classes, bool allowed = true) {
+  const int s = kt < max_parameters ? kt : max_parameters;
+  return allowed && elem_size == 4 && s > 0 && s * n_classes <= 16 ? s : 0;
+}
+// Rows per lane of the parametric builds: this (the plain kernel's preferred count) and 1.
+constexpr int sr_grad_param_rows(int elem_size, int kt) {
+  return elem_size == 8 && sr_grad_rows_per_lane(kt) > 1 ? sr_grad_rows_per_lane(kt) / 2 : sr_grad_rows_per_lane(kt);
+}
+// As sr_grad_launch_rows over that set (class row and bins in the LDS): `force` when it is one of the
+// two and fits; the preferred count while two workgroups share a CU, else 1; 0 when 1 does not fit.
+inline int sr_grad_param_launch_rows(int elem_size, int kt, int nf, bool weighted, int stack_depth, int waves,
+                                     size_t lds_max, int n_classes, int lane_slots, int force = 0) {
+  const int pref = sr_grad_param_rows(elem_size, kt);
+  auto fits = [&](int r, size_t cap) {
+    return sr_grad_lds_bytes(elem_size, kt, r, nf, weighted, stack_depth, waves, n_classes, lane_slots) <= cap;
+  };
+  if (force > 0 && (force == 1 || force == pref) && fits(force, lds_max)) return force;
+  if (fits(pref, lds_max / 2)) return pref;
+  return fits(1, lds_max) ? 1 : 0;
+}
+template <typename T, bool GATHER>
+hipError_t sr_launch_grad_param_any(const SrGradArgs<T>& a, const SrGradParamArgs<T>& p, int kt, int rows, int n_blocks,
+                                    hipStream_t s);
 // The reference's loss fold in row order for listed trees (sr_fold.h; sr_aux.hip): predictions
 // pred[b][pred_ld] of n rows, losses against y (and w) at row_idx (or the row itself).
 // sr_launch_fold_segsum: per segment of seg_len rows, segsum[b][seg] = the f64 sum of its losses;

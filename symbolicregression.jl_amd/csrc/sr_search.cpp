@@ -42,6 +42,7 @@
 #include "sr_compile.h"
 #include "sr_constopt.h"
 #include "sr_libm.h"
+#include "sr_param_pack.h"
 #include "sr_search_tree.h"
 
 int sr_set_error(int code, const std::string& msg);  // sr_capi.cpp
@@ -1469,6 +1470,168 @@ int optimize_common(Scorer<T>& sc, const sr_tree_batch* trees, const int64_t* ro
   return SR_OK;
 }
 
+// The BFGS objective over a batch of ParametricExpression trees, beside TreeObjective: item k = tree k with
+// x = [its constants in pre-order; vec(parameters)] (sr_param_pack.h) rounded to T, one batched parametric
+// device call per evaluation round.
+template <typename T>
+struct ParamObjective : SrObjective {
+  sr_ctx* ctx = nullptr;
+  const sr_dataset* ds = nullptr;
+  int opset_id = 0, loss_code = 0;
+  const sr_tree_batch* trees = nullptr;
+  const sr_param_batch* params = nullptr;
+  const int64_t* row_idx = nullptr;
+  int64_t n_idx = 0;
+  std::vector<int64_t> f_calls;
+  // the sub-batch of one round
+  std::vector<int64_t> offs;
+  std::vector<uint8_t> degree, op, constant, isp;
+  std::vector<uint16_t> feature, par;
+  std::vector<T> val, mats;
+  size_t kc() const { return size_t(params->max_parameters) * size_t(params->n_classes); }
+  void build(const std::vector<int>& items, const std::vector<std::vector<double>>& xs, sr_tree_batch* tb, sr_param_batch* pb) {
+    offs.assign(1, 0);
+    degree.clear(), op.clear(), constant.clear(), isp.clear(), feature.clear(), par.clear(), val.clear();
+    mats.assign(items.size() * kc(), T(0));
+    const T* vals = static_cast<const T*>(trees->val);
+    for (size_t j = 0; j < items.size(); ++j) {
+      const int64_t t = items[j];
+      size_t q = 0;
+      for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i) {
+        degree.push_back(trees->degree[i]);
+        op.push_back(trees->op[i]);
+        feature.push_back(trees->feature[i]);
+        constant.push_back(trees->constant[i]);
+        isp.push_back(params->is_parameter[i]);
+        par.push_back(params->parameter[i]);
+        const bool c = trees->degree[i] == 0 && trees->constant[i];
+        val.push_back(c ? T(xs[j][q]) : vals[i]);
+        q += c ? 1 : 0;
+      }
+      offs.push_back(int64_t(degree.size()));
+      for (size_t m = 0; m < kc(); ++m) mats[j * kc() + m] = T(xs[j][q + m]);
+    }
+    *tb = sr_tree_batch{};
+    tb->n_trees = int64_t(items.size());
+    tb->offsets = offs.data();
+    tb->degree = degree.data();
+    tb->op = op.data();
+    tb->feature = feature.data();
+    tb->constant = constant.data();
+    tb->val = val.data();
+    *pb = sr_param_batch{isp.data(), par.data(), params->max_parameters, params->n_classes, mats.data()};
+  }
+  int f(const std::vector<int>& items, const std::vector<std::vector<double>>& xs, std::vector<double>* out) override {
+    sr_tree_batch tb;
+    sr_param_batch pb;
+    build(items, xs, &tb, &pb);
+    if (counting)
+      for (int k : items) ++f_calls[size_t(k)];
+    std::vector<T> loss(items.size());
+    std::vector<uint8_t> comp(items.size());
+    const int rc = sr_eval_loss_batch_parametric(ctx, ds, opset_id, &tb, &pb, row_idx, n_idx, loss_code, loss.data(), comp.data());
+    if (rc) return rc;
+    out->resize(items.size());
+    for (size_t j = 0; j < items.size(); ++j) (*out)[j] = comp[j] ? double(loss[j]) : INFINITY;
+    return SR_OK;
+  }
+  int fg(const std::vector<int>& items, const std::vector<std::vector<double>>& xs, std::vector<double>* out,
+         std::vector<std::vector<double>>* grads) override {
+    sr_tree_batch tb;
+    sr_param_batch pb;
+    build(items, xs, &tb, &pb);
+    size_t n = 0;
+    for (size_t j = 0; j < items.size(); ++j) {
+      if (counting) ++f_calls[size_t(items[j])];
+      n += xs[j].size();
+    }
+    std::vector<T> loss(items.size()), g(n + 1, T(0));
+    std::vector<uint8_t> comp(items.size());
+    const int rc = sr_eval_grad_batch_parametric(ctx, ds, opset_id, &tb, &pb, row_idx, n_idx, loss_code, loss.data(),
+                                                 g.data(), comp.data());
+    if (rc) return rc;
+    out->resize(items.size());
+    grads->resize(items.size());
+    size_t at = 0;
+    for (size_t j = 0; j < items.size(); ++j) {
+      (*out)[j] = comp[j] ? double(loss[j]) : INFINITY;
+      (*grads)[j].assign(xs[j].size(), 0.0);
+      for (size_t q = 0; q < xs[j].size(); ++q) (*grads)[j][q] = double(g[at + q]);
+      at += xs[j].size();
+    }
+    return SR_OK;
+  }
+};
+
+template <typename T>
+int optimize_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                        const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind, int iterations,
+                        int64_t f_calls_limit, int nrestarts, uint64_t seed, void* out_consts, void* out_params,
+                        void* out_loss, uint8_t* out_improved, int64_t* out_f_calls) {
+  const int64_t nt = trees->n_trees;
+  ParamObjective<T> obj;
+  obj.ctx = ctx;
+  obj.ds = ds;
+  obj.opset_id = opset_id;
+  obj.loss_code = loss_kind;
+  obj.trees = trees;
+  obj.params = params;
+  obj.row_idx = row_idx && n_idx > 0 ? row_idx : nullptr;
+  obj.n_idx = row_idx && n_idx > 0 ? n_idx : 0;
+  obj.f_calls.assign(size_t(nt), 0);
+  const size_t kc = obj.kc();
+  const T* vals = static_cast<const T*>(trees->val);
+  const T* pm = static_cast<const T*>(params->parameters);
+  // x0 = [constants; vec(P)] per tree, and the restarts x0 .* (1 + eps / 2) over the whole vector, drawn
+  // per tree then per restart as the plain optimiser draws them
+  std::vector<std::vector<double>> x0(static_cast<size_t>(nt));
+  std::vector<size_t> ncs(static_cast<size_t>(nt));
+  for (int64_t t = 0; t < nt; ++t) {
+    std::vector<T> c;
+    for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i)
+      if (trees->degree[i] == 0 && trees->constant[i]) c.push_back(vals[i]);
+    ncs[size_t(t)] = c.size();
+    srpp::pack<T>(c.data(), c.size(), kc ? pm + size_t(t) * kc : nullptr, kc, &x0[size_t(t)]);
+  }
+  SrRng rng;
+  rng.seed(seed, 0x6f7074696d697a65ull);
+  std::vector<std::vector<std::vector<double>>> restarts(static_cast<size_t>(nrestarts),
+                                                         std::vector<std::vector<double>>(static_cast<size_t>(nt)));
+  for (int64_t t = 0; t < nt; ++t)
+    for (int r = 0; r < nrestarts; ++r) srpp::draw_restart<T>(rng, x0[size_t(t)], &restarts[size_t(r)][size_t(t)]);
+  std::vector<std::vector<double>> bx;
+  std::vector<double> bf, base;
+  int rc = sr_optimize_batch(obj, x0, restarts, iterations, &bx, &bf, &base, f_calls_limit);
+  if (rc) return rc;
+  // the loss at the adopted vectors: one more batched call, f(result.minimizer)
+  std::vector<int> better;
+  std::vector<std::vector<double>> xb;
+  for (int64_t t = 0; t < nt; ++t)
+    if (bf[size_t(t)] < base[size_t(t)]) {
+      better.push_back(int(t));
+      xb.push_back(bx[size_t(t)]);
+    }
+  std::vector<double> lb;
+  if (!better.empty()) {
+    obj.counting = false;
+    rc = obj.f(better, xb, &lb);
+    obj.counting = true;
+    if (rc) return rc;
+  }
+  size_t at = 0, jb = 0;
+  for (int64_t t = 0; t < nt; ++t) {
+    const bool imp = jb < better.size() && better[jb] == int(t);
+    const std::vector<double>& x = imp ? bx[size_t(t)] : x0[size_t(t)];
+    srpp::unpack<T>(x, ncs[size_t(t)], static_cast<T*>(out_consts) + at, static_cast<T*>(out_params) + size_t(t) * kc, kc);
+    at += ncs[size_t(t)];
+    static_cast<T*>(out_loss)[t] = imp ? T(lb[jb]) : T(base[size_t(t)]);
+    out_improved[t] = imp ? 1 : 0;
+    out_f_calls[t] = obj.f_calls[size_t(t)];
+    jb += imp ? 1 : 0;
+  }
+  return SR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1747,6 +1910,34 @@ int sr_optimize_constants_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id,
                               out_loss, out_improved, out_f_calls);
   };
   return dt == SR_DTYPE_F32 ? run(0.0f) : run(0.0);
+}
+
+int sr_optimize_constants_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                           const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx,
+                                           int loss_kind, int iterations, int64_t f_calls_limit, int nrestarts,
+                                           uint64_t seed, void* out_consts, void* out_params, void* out_loss,
+                                           uint8_t* out_improved, int64_t* out_f_calls) {
+  if (!ctx || !ds || !trees || !params) return sr_set_error(SR_ERR_INVALID_ARG, "NULL context, dataset, trees or parameters");
+  if (iterations < 0 || nrestarts < 0 || f_calls_limit < 0)
+    return sr_set_error(SR_ERR_INVALID_ARG, "negative iterations / f_calls_limit / restarts");
+  const int64_t nt = trees->n_trees;
+  if (nt < 0) return sr_set_error(SR_ERR_INVALID_ARG, "negative tree count");
+  if (nt == 0) return SR_OK;
+  if (params->max_parameters < 0 || params->max_parameters > 65535 || params->n_classes < 1)
+    return sr_set_error(SR_ERR_INVALID_ARG, "bad max_parameters / n_classes");
+  if (!trees->offsets || !trees->degree || !trees->op || !trees->feature || !trees->constant || !trees->val ||
+      !params->is_parameter || !params->parameter || (params->max_parameters > 0 && (!params->parameters || !out_params)) ||
+      !out_consts || !out_loss || !out_improved || !out_f_calls)
+    return sr_set_error(SR_ERR_INVALID_ARG, "NULL arrays");
+  int dt = 0;
+  int64_t nf = 0, n = 0;
+  const int rc = sr_dataset_info(ds, &dt, &nf, &n);
+  if (rc) return rc;
+  if (dt == SR_DTYPE_F32)
+    return optimize_parametric<float>(ctx, ds, opset_id, trees, params, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
+                                      nrestarts, seed, out_consts, out_params, out_loss, out_improved, out_f_calls);
+  return optimize_parametric<double>(ctx, ds, opset_id, trees, params, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
+                                     nrestarts, seed, out_consts, out_params, out_loss, out_improved, out_f_calls);
 }
 
 int sr_optimize_constants_callbacks(int dtype, const sr_tree_batch* trees, const int64_t* row_idx, int64_t n_idx,

@@ -509,6 +509,8 @@ function optimize_constants_batch!(dataset::Dataset{T,L}, members::AbstractVecto
     limits === nothing && return nothing
     iterations, f_calls_limit = limits
     trees = [m.tree for m in members]
+    all(parametric_tree, trees) &&
+        return optimize_constants_batch_parametric!(dataset, members, options, iterations, f_calls_limit)
     all(device_tree, trees) || return nothing
     ctx = context()
     oid = opset_id(ctx, get_operators(first(trees), options))
@@ -547,6 +549,70 @@ function optimize_constants_batch!(dataset::Dataset{T,L}, members::AbstractVecto
         num_evals[k] = f_calls[k] * frac
         if improved[k] == 0x01
             set_scalar_constants!(m.tree, consts[at+1:at+nk], refs)
+            m.loss = L(losses[k]) + LossFunctionsModule.dimensional_regularization(m.tree, dataset, base)
+            m.cost = LossFunctionsModule.loss_to_cost(m.loss, dataset.use_baseline, dataset.baseline_loss, m, base)
+            m.birth = SymbolicRegression.UtilsModule.get_birth_order(; deterministic=base.deterministic)
+            num_evals[k] += frac
+        end
+        at += nk
+    end
+    return num_evals
+end
+
+"""The same for `ParametricExpression` members: ONE `sr_optimize_constants_batch_parametric` call fits
+`x = vcat(constants, parameters[:])` of every member — exactly what `get_scalar_constants(::ParametricExpression)`
+hands Optim (count_constants_for_optimization = constants + length(parameters),
+src/ParametricExpression.jl:169-171) — and writes the adopted constants AND `get_metadata(ex).parameters`
+back through `set_scalar_constants!`.  `nothing` (the reference's per-member CPU path) for a dataset without
+classes, matrices of different sizes, or any non-OK return of the library."""
+function optimize_constants_batch_parametric!(dataset::Dataset{T,L}, members::AbstractVector, options::MI355XOptions,
+                                              iterations, f_calls_limit) where {T,L}
+    trees = [m.tree for m in members]
+    full = SymbolicRegression.CoreModule.get_full_dataset(dataset)
+    cls = dataset_classes(full)
+    cls === nothing && return nothing
+    ctx = context()
+    oid = opset_id(ctx, get_operators(first(trees), options))
+    lk = loss_kind(options)
+    (oid === nothing || lk === nothing) && return nothing
+    idx = SymbolicRegression.CoreModule.get_indices(dataset)
+    f = flatten(trees, T)
+    p = flatten_parameters(trees, T)
+    (p === nothing || p.n_classes != maximum(cls)) && return nothing
+    n = length(trees)
+    kc = Int(p.max_parameters) * Int(p.n_classes)
+    consts = Vector{T}(undef, max(1, count(==(0x01), f.constant)))
+    params = Vector{T}(undef, max(1, n * kc))   # per tree (max_parameters, n_classes) column-major, as p.mats
+    losses = Vector{T}(undef, n)
+    improved = Vector{UInt8}(undef, n)
+    f_calls = Vector{Int64}(undef, n)
+    rows = idx === nothing ? nothing : Int64.(idx .- 1)
+    dsh = device_dataset(ctx, full)
+    seed = rand(UInt64)
+    GC.@preserve f p rows consts params losses improved f_calls begin
+        b = SrTreeBatch(n, pointer(f.offsets), pointer(f.degree), pointer(f.op), pointer(f.feature),
+                        pointer(f.constant), Ptr{Cvoid}(pointer(f.val)))
+        pb = SrParamBatch(pointer(p.is_parameter), pointer(p.parameter), p.max_parameters, p.n_classes,
+                          Ptr{Cvoid}(pointer(p.mats)))
+        rc = ccall((:sr_optimize_constants_batch_parametric, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{SrTreeBatch}, Ref{SrParamBatch}, Ptr{Int64}, Int64, Cint, Cint,
+                    Int64, Cint, UInt64, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{UInt8}, Ptr{Int64}),
+                   ctx.handle, dsh, oid, b, pb, rows === nothing ? C_NULL : pointer(rows),
+                   rows === nothing ? 0 : length(rows), lk, iterations, f_calls_limit,
+                   options.optimizer_nrestarts, seed, consts, params, losses, improved, f_calls)
+        rc == 0 || return nothing   # (any failure: the reference's CPU optimize_constants takes the members)
+    end
+    base = options.base
+    frac = SymbolicRegression.CoreModule.dataset_fraction(dataset)
+    num_evals = zeros(Float64, n)
+    at = 0
+    for (k, m) in enumerate(members)
+        x0, refs = get_scalar_constants(m.tree)   # vcat(constants in pre-order, parameters[:])
+        nk = length(x0) - kc
+        num_evals[k] = f_calls[k] * frac
+        if improved[k] == 0x01
+            x = vcat(consts[at+1:at+nk], params[(k-1)*kc+1:k*kc])
+            set_scalar_constants!(m.tree, x, refs)   # constants and get_metadata(m.tree).parameters
             m.loss = L(losses[k]) + LossFunctionsModule.dimensional_regularization(m.tree, dataset, base)
             m.cost = LossFunctionsModule.loss_to_cost(m.loss, dataset.use_baseline, dataset.baseline_loss, m, base)
             m.birth = SymbolicRegression.UtilsModule.get_birth_order(; deterministic=base.deterministic)

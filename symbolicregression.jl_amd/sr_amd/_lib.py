@@ -98,6 +98,9 @@ EXPORTED_SYMBOLS = (
     "sr_eval_loss_batch_views_parametric",
     "sr_eval_tree_array_parametric",
     "sr_compile_info_parametric",
+    "sr_eval_grad_batch_parametric",
+    "sr_eval_grad_batch_views_parametric",
+    "sr_optimize_constants_batch_parametric",
 )
 
 # mutation kinds in sr_search_options.mutation_weights order (SR_MUT_*)
@@ -223,6 +226,19 @@ def _load():
         "sr_eval_tree_array_parametric": (
             c_int,
             [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int64, P, P],
+        ),
+        "sr_eval_grad_batch_parametric": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int64, c_int, P, P, P],
+        ),
+        "sr_eval_grad_batch_views_parametric": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int, P, c_int64, c_int, P, P, P],
+        ),
+        "sr_optimize_constants_batch_parametric": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int64, c_int, c_int, c_int64, c_int,
+             ctypes.c_uint64, P, P, P, P, P],
         ),
         "sr_compile_info_parametric": (
             c_int,

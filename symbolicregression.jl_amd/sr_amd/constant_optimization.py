@@ -40,6 +40,12 @@ def optimize_constants_batch(trees, dataset, options, rng=None, *, iterations=No
     default to the options' ``optimizer_iterations`` / ``optimizer_f_calls_limit`` (Optim.Options,
     src/Options.jl:988-997); a non-BFGS ``optimizer_algorithm`` raises NotImplementedError (the
     reference's CPU optimiser is the caller's path for it).
+
+    A parametric batch (ParametricExpression trees on a dataset with classes) is fitted as the reference
+    fits it: the vector is ``TreeBatch.get_scalar_constants()`` per tree, the constants followed by the
+    whole ``(max_parameters, n_classes)`` matrix, and the returned batch carries the adopted constants
+    and parameters (``sr_optimize_constants_batch_parametric``).  A plain batch takes
+    ``sr_optimize_constants_batch`` as before.
     """
     from .loss import _as_batch
 
@@ -62,6 +68,25 @@ def optimize_constants_batch(trees, dataset, options, rng=None, *, iterations=No
     rows = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
     p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
     s = tb.to_struct()
+    if tb.parametric:
+        # ParametricExpression trees: x = [constants; vec(parameters)] is what the optimiser fits (the
+        # reference's get_scalar_constants), so the adopted parameters come back with the constants
+        from .loss import _param_struct
+
+        ps = _param_struct(tb, full, options)
+        K, C = int(tb.parameters.shape[1]), int(tb.parameters.shape[2])
+        mats = np.zeros((max(1, nt), C, max(1, K)), dtype=full.dtype)  # (Julia's column-major layout per tree)
+        _lib.check(_lib.lib.sr_optimize_constants_batch_parametric(
+            ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), ctypes.byref(ps),
+            p(rows), 0 if rows is None else rows.size, ctx.loss_code(options), int(iterations), int(f_calls_limit),
+            int(nrestarts), ctypes.c_uint64(seed), p(consts), p(mats), p(losses), p(improved), p(f_calls)))
+        n_const = int(np.count_nonzero(tb.constant_mask()))
+        new_tb = tb.with_constants(consts[:n_const])
+        if K > 0:
+            new_tb.parameters = np.ascontiguousarray(mats[:nt].transpose(0, 2, 1))
+        imp = improved[:nt].astype(bool)
+        num_evals = (f_calls[:nt] + imp.astype(np.int64)) * dataset.dataset_fraction()
+        return new_tb, losses[:nt].copy(), imp, num_evals
     _lib.check(_lib.lib.sr_optimize_constants_batch(
         ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), p(rows),
         0 if rows is None else rows.size, ctx.loss_code(options), int(iterations), int(f_calls_limit), int(nrestarts),

@@ -119,15 +119,19 @@ def eval_grad_batch_views(trees, dataset, options, tree_view, view_rows, *, ctx=
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
-    if tb.parametric:
-        raise NotImplementedError("gradients of ParametricExpression trees are not on the device path")
     nt = tb.n_trees
     tv, vr = _views(tree_view, view_rows, nt)
     losses = np.empty(nt, dtype=full.dtype)
     complete = np.empty(nt, dtype=np.uint8)
-    grads = np.zeros(int(tb.constant_mask().sum()) + 1, dtype=full.dtype)
+    grads = np.zeros(int(tb.scalar_offsets()[-1]) + 1, dtype=full.dtype)
     s = tb.to_struct()
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    if tb.parametric:
+        ps = _param_struct(tb, full, options)
+        _lib.check(_lib.lib.sr_eval_grad_batch_views_parametric(
+            ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), ctypes.byref(ps),
+            p(tv), int(vr.shape[0]), p(vr), int(vr.shape[1]), ctx.loss_code(options), p(losses), p(grads), p(complete)))
+        return losses, grads[:-1], complete.astype(bool)
     _lib.check(_lib.lib.sr_eval_grad_batch_views(
         ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), p(tv), int(vr.shape[0]),
         p(vr), int(vr.shape[1]), ctx.loss_code(options), p(losses), p(grads), p(complete)))
@@ -138,7 +142,10 @@ def eval_grad_batch(trees, dataset, options, *, ctx=None):
     """Loss and its gradient with respect to every tree's constants, for a whole batch.
 
     Returns ``(losses[T], grads[T], complete[bool])``; ``grads`` holds each tree's constants in
-    pre-order (``get_scalar_constants``) at ``TreeBatch.constant_offsets()``.  This is the
+    pre-order (``get_scalar_constants``) at ``TreeBatch.constant_offsets()``; for a parametric batch each
+    tree's constants are followed by its ``max_parameters x n_classes`` parameter entries, column-major
+    (``TreeBatch.scalar_offsets()`` / ``split_scalars``; exactly 0 for an unused parameter and for a class
+    with no row).  This is the
     objective/gradient pair of reference src/ConstantOptimization.jl:126-167 (``Evaluator`` /
     ``GradEvaluator`` with a forward-mode backend) computed on the device by forward-mode dual
     numbers; an incomplete tree has loss ``Inf`` and a zero gradient (``eval_loss`` is the
@@ -149,14 +156,20 @@ def eval_grad_batch(trees, dataset, options, *, ctx=None):
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
-    if tb.parametric:
-        raise NotImplementedError("gradients of ParametricExpression trees are not on the device path")
     nt = tb.n_trees
     losses = np.empty(nt, dtype=full.dtype)
     complete = np.empty(nt, dtype=np.uint8)
-    grads = np.zeros(int(tb.constant_mask().sum()) + 1, dtype=full.dtype)
+    grads = np.zeros(int(tb.scalar_offsets()[-1]) + 1, dtype=full.dtype)
     idx = dataset.indices
     s = tb.to_struct()
+    if tb.parametric:  # ParametricExpression trees: [constants | parameters column-major] per tree
+        ps = _param_struct(tb, full, options)
+        _lib.check(_lib.lib.sr_eval_grad_batch_parametric(
+            ctx.handle, full.device_handle(ctx), ctx.opset_id(options.operators), ctypes.byref(s), ctypes.byref(ps),
+            None if idx is None else idx.ctypes.data_as(ctypes.c_void_p), 0 if idx is None else int(idx.size),
+            ctx.loss_code(options), losses.ctypes.data_as(ctypes.c_void_p), grads.ctypes.data_as(ctypes.c_void_p),
+            complete.ctypes.data_as(ctypes.c_void_p)))
+        return losses, grads[:-1], complete.astype(bool)
     _lib.check(
         _lib.lib.sr_eval_grad_batch(
             ctx.handle,

@@ -389,6 +389,60 @@ class TreeBatch:
         val[self.constant_mask()] = np.asarray(consts, dtype=val.dtype)
         return self._sel(self.offsets, slice(None), slice(None), val)
 
+    # The scalars the optimiser fits and the gradient calls differentiate: a plain tree's constants; for a
+    # ParametricExpression tree DynamicExpressions' get_scalar_constants order, the constants in pre-order
+    # followed by vec(parameters) column-major (entry (k-1) + max_parameters (c-1): ``parameters[t].T.ravel()``),
+    # every entry present whether the tree uses it or not.
+    def scalar_offsets(self) -> np.ndarray:
+        """[n_trees + 1]: where each tree's scalars start in ``get_scalar_constants()`` / a flat gradient
+        (``constant_offsets()`` for a plain batch)."""
+        c = self.constant_offsets()
+        if not self.parametric:
+            return c
+        kc = int(self.parameters.shape[1]) * int(self.parameters.shape[2])
+        return c + kc * np.arange(self.n_trees + 1, dtype=np.int64)
+
+    def get_scalar_constants(self) -> np.ndarray:
+        """All trees' scalars, concatenated (see ``scalar_offsets``)."""
+        if not self.parametric:
+            return self.get_constants()
+        c, co = self.get_constants(), self.constant_offsets()
+        so = self.scalar_offsets()
+        x = np.empty(int(so[-1]), dtype=self.val.dtype)
+        for t in range(self.n_trees):
+            nc = int(co[t + 1] - co[t])
+            x[so[t]:so[t] + nc] = c[co[t]:co[t + 1]]
+            x[so[t] + nc:so[t + 1]] = self.parameters[t].T.ravel()
+        return x
+
+    def split_scalars(self, flat):
+        """A flat vector in the ``scalar_offsets`` layout (scalars or a gradient) -> (the constants' part,
+        concatenated as ``get_constants``; the parameters' part as ``[n_trees, max_parameters, n_classes]``,
+        None for a plain batch)."""
+        flat = np.asarray(flat)
+        if not self.parametric:
+            return flat.copy(), None
+        co, so = self.constant_offsets(), self.scalar_offsets()
+        if flat.shape != (int(so[-1]),):
+            raise ValueError(f"expected {int(so[-1])} scalars, got {flat.shape}")
+        K, C = int(self.parameters.shape[1]), int(self.parameters.shape[2])
+        consts = np.empty(int(co[-1]), dtype=flat.dtype)
+        mats = np.empty((self.n_trees, K, C), dtype=flat.dtype)
+        for t in range(self.n_trees):
+            nc = int(co[t + 1] - co[t])
+            consts[co[t]:co[t + 1]] = flat[so[t]:so[t] + nc]
+            mats[t] = flat[so[t] + nc:so[t + 1]].reshape(C, K).T
+        return consts, mats
+
+    def with_scalar_constants(self, x) -> "TreeBatch":
+        """Same trees with their scalars replaced (set_scalar_constants! for the whole batch)."""
+        if not self.parametric:
+            return self.with_constants(x)
+        consts, mats = self.split_scalars(np.asarray(x, dtype=self.val.dtype))
+        out = self.with_constants(consts)
+        out.parameters = np.ascontiguousarray(mats, dtype=self.val.dtype)
+        return out
+
     def subset(self, idx) -> "TreeBatch":
         idx = np.asarray(idx, dtype=np.int64)
         starts, ends = self.offsets[idx], self.offsets[idx + 1]
