@@ -131,6 +131,38 @@ int sr_register_opset(sr_ctx* ctx, int n_unary, const char* const* unary_names, 
 int sr_register_loss(sr_ctx* ctx, int kind, double param, int* loss_code);
 
 /*
+ * Register an elementwise loss given as an expression — the reference's `elementwise_loss = (x, y) -> ...` /
+ * `(x, y, w) -> ...` (src/LossFunctions.jl:38-58), which the device cannot take as a closure.  `tree` is a
+ * sr_tree_batch of exactly ONE tree whose leaves are feature 1 = prediction, 2 = target, 3 = weight, and
+ * constants — `val` is Float64 here, whatever the datasets' type — over the operators named by unary_names /
+ * binary_names (resolved as sr_register_opset resolves them; any operator of the device catalog,
+ * independent of the search's own operator set).  It is compiled for both element types (constants rounded to
+ * T, constant subtrees folded in T, all arithmetic in T) and uploaded; *loss_code is accepted as `loss_kind`
+ * by sr_eval_loss_batch(_views), sr_eval_grad_batch(_views), sr_optimize_constants_batch and
+ * sr_search_use_device / sr_search_add_device, on plain trees.  The parametric, sharded, partials and jsum
+ * calls return SR_ERR_INVALID_ARG for such a code.
+ * A weighted dataset hands w[i] to the expression and the loss is sum(L(pred, y, w)) / sum(w) — no further
+ * multiplication by w; an expression that references the weight on an unweighted dataset, or does not on a
+ * weighted one (Julia: MethodError), is SR_ERR_INVALID_ARG at the call.
+ * A complete tree's loss is the f64 sum of the T element values divided by n (or the f64 sum of w), rounded
+ * to T once — NaN or +-Inf when that sum is; the in-order Float32 fold ("ref_fold") does not apply: an
+ * expression may be negative.  Limits: 127 nodes, 64 instructions after folding, 4 live values (every tree
+ * of up to 31 nodes needing at most 4 is inside them); beyond: SR_ERR_INVALID_ARG.  SR_ERR_UNSUPPORTED_OP
+ * for an operator outside the catalog.  Registering the same expression again returns the same code.
+ */
+int sr_register_loss_expr(sr_ctx* ctx, int n_unary, const char* const* unary_names, int n_binary,
+                          const char* const* binary_names, const sr_tree_batch* tree, int* loss_code);
+/*
+ * The same compiler and the host's interpreter, without a context (no device needed; the kernels run the same
+ * header): out_value[i] = L(pred[i], y[i], w[i]) and, when out_dvalue is not NULL, d L / d pred there by
+ * forward mode (sr_unary_deriv / sr_binary_partials per node, their kink conventions), for n values of dtype;
+ * w is NULL exactly when the expression does not reference the weight.
+ */
+int sr_loss_expr_host(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                      const char* const* binary_names, const sr_tree_batch* tree, int64_t n, const void* pred,
+                      const void* y, const void* w, void* out_value, void* out_dvalue);
+
+/*
  * Upload a dataset (src/Dataset.jl:131-246).  X is Julia's column-major [nfeatures, n] matrix
  * (address f + nfeatures*i); the device copy is transposed to per-feature contiguous rows.
  * y has n entries; weights may be NULL (unweighted).  dtype is SR_DTYPE_F32 / SR_DTYPE_F64.

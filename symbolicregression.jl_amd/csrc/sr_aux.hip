@@ -1587,9 +1587,33 @@ hipError_t sr_launch_loss_cand(const SrEvalArgs<T>& a, int R, int waves, int n_b
 template hipError_t sr_launch_loss_cand<float>(const SrEvalArgs<float>&, int, int, int, hipStream_t);
 template hipError_t sr_launch_loss_cand<double>(const SrEvalArgs<double>&, int, int, int, hipStream_t);
 
+// The kernels of expression-loss calls (sr_inst_*lossx*.hip): the classic kernel at its default rows per
+// lane, 4 waves, full view or gathered, per tier.
+template <typename T>
+hipError_t sr_launch_eval_lossx(const SrEvalArgs<T>& a, bool gather, int tier, int R, int waves, bool vstk, int n_blocks,
+                                hipStream_t s) {
+  constexpr int RB = sizeof(T) == 4 ? 8 : 4;  // BASIC classic rows per lane
+  constexpr int RF = sizeof(T) == 4 ? 4 : 2;  // FULL tier rows per lane
+  if (a.loss_kind != SR_LOSS_EXPR || a.lx_code == nullptr || a.lx_n < 1 || a.lx_n > SR_LX_MAX_INS) return hipErrorInvalidValue;
+  if (vstk || waves != 4) return hipErrorInvalidValue;
+  if (tier == SR_TIER_BASIC) {
+    if (R != RB) return hipErrorInvalidValue;
+    return gather ? sr_launch_tile<T, RB, SR_MODE_LOSS, true, SR_TIER_BASIC, 4, SR_LOSS_EXPR>(a, n_blocks, s)
+                  : sr_launch_tile<T, RB, SR_MODE_LOSS, false, SR_TIER_BASIC, 4, SR_LOSS_EXPR>(a, n_blocks, s);
+  }
+  if (R != RF) return hipErrorInvalidValue;
+  return gather ? sr_launch_tile<T, RF, SR_MODE_LOSS, true, SR_TIER_FULL, 4, SR_LOSS_EXPR>(a, n_blocks, s)
+                : sr_launch_tile<T, RF, SR_MODE_LOSS, false, SR_TIER_FULL, 4, SR_LOSS_EXPR>(a, n_blocks, s);
+}
+template hipError_t sr_launch_eval_lossx<float>(const SrEvalArgs<float>&, bool, int, int, int, bool, int, hipStream_t);
+template hipError_t sr_launch_eval_lossx<double>(const SrEvalArgs<double>&, bool, int, int, int, bool, int, hipStream_t);
+
 template <typename T>
 hipError_t sr_launch_eval(const SrEvalArgs<T>& a, int mode, bool gather, int tier, int R, int waves, bool vstk,
                           int n_blocks, hipStream_t s) {
+  // an expression loss: its own builds or an error, never a generic-loss kernel (whose default case is L2)
+  if (a.loss_kind == SR_LOSS_EXPR && mode == SR_MODE_LOSS) return sr_launch_eval_lossx<T>(a, gather, tier, R, waves, vstk, n_blocks, s);
+  if (a.loss_kind == SR_LOSS_EXPR && mode == SR_MODE_FOLD) return hipErrorInvalidValue;
   if constexpr (sizeof(T) == 4) {
     if (mode == SR_MODE_FOLD) {  // (the launch shapes of the loss launches a large call runs: sr_inst_f32_fold*.hip)
       const bool l2 = a.loss_kind == SR_LOSS_L2;

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -108,6 +109,12 @@ struct HostBuf {
 };
 
 constexpr int kLossCodeBase = 256;
+// expression losses (sr_register_loss_expr): code = kLossExprBase + index
+constexpr int kLossExprBase = 1 << 20;
+const char* const kLossExprOnly =
+    "an expression loss (sr_register_loss_expr) is taken by sr_eval_loss_batch(_views), sr_eval_grad_batch(_views), "
+    "sr_optimize_constants_batch and the native search on plain trees only: not by the parametric, sharded, partials "
+    "or jsum calls";
 
 // Parameter-free losses (and HuberLoss with its default delta = 1) may be passed by kind.
 inline bool loss_direct_ok(int kind) {
@@ -231,6 +238,27 @@ struct sr_ctx {
   std::vector<SrOpset> opsets;
   std::vector<int> tiers;
   std::vector<std::pair<int, double>> losses;  // registered (kind, param); code = kLossCodeBase + index
+  // expression losses (sr_register_loss_expr; code = kLossExprBase + index): the registration's bytes (the
+  // same expression again gets the same code), the program per element type (sr_loss_expr.h) and their
+  // device copies — one small buffer, uploaded once: the Float32 instructions, then the Float64 ones
+  struct LossExpr {
+    std::string key;
+    SrLossProg<float> p32;
+    SrLossProg<double> p64;
+    void* dev = nullptr;
+    template <typename T>
+    const SrLossProg<T>& prog() const {
+      if constexpr (sizeof(T) == 4) return p32;
+      else return p64;
+    }
+    template <typename T>
+    SrLossProgArgs<T> args() const {
+      const char* d = static_cast<const char*>(dev);
+      if constexpr (sizeof(T) == 4) return SrLossProgArgs<T>{reinterpret_cast<const SrIns<T>*>(d), p32.n};
+      else return SrLossProgArgs<T>{reinterpret_cast<const SrIns<T>*>(d + sizeof(p32.ins)), p64.n};
+    }
+  };
+  std::deque<LossExpr> loss_exprs;  // (a deque: a call keeps a pointer to its entry while others register)
   DevBuf prog, outs, part_sum, part_flag, pred, row_idx, tree_list,
       range_lo, range_hi, range_sums, packed, hint, jsum_prog, jsum_scratch, probe_sum, probe_flag, g_code, g_offsets, g_consts, g_const_off, g_items, g_part, g_out,
       derived_cols, probe_derived, fold_io;
@@ -488,7 +516,19 @@ int validate_common(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tr
 }
 
 // loss_kind as passed to the eval calls -> (SrLossKind, parameter).
-int decode_loss(sr_ctx* ctx, int code, int* kind, double* param) {
+// expr: where the call takes expression losses, receives the registered one (NULL otherwise); a call that
+// passes none refuses their codes.
+int decode_loss(sr_ctx* ctx, int code, int* kind, double* param, const sr_ctx::LossExpr** expr = nullptr) {
+  if (expr) *expr = nullptr;
+  if (code >= kLossExprBase) {
+    const size_t i = size_t(code - kLossExprBase);
+    if (i >= ctx->loss_exprs.size()) return set_error(SR_ERR_INVALID_ARG, "unknown expression loss code " + std::to_string(code));
+    if (!expr) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
+    *kind = SR_LOSS_EXPR;
+    *param = 0.0;
+    *expr = &ctx->loss_exprs[i];
+    return SR_OK;
+  }
   if (code >= kLossCodeBase) {
     const size_t i = size_t(code - kLossCodeBase);
     if (i >= ctx->losses.size()) return set_error(SR_ERR_INVALID_ARG, "unknown registered loss code " + std::to_string(code));
@@ -521,8 +561,22 @@ struct ViewSpec {
 };
 
 // Rows of the reference's loss fold for the overflow rule (sr_fold.h), or 0 when the rule does not
-// apply (negative weights: the fold is not monotone).
-inline int64_t fold_terms(const sr_dataset* ds, int64_t n_rows) { return (ds->w && ds->w_min < 0.0) ? 0 : n_rows; }
+// apply (negative weights: the fold is not monotone; an expression loss, which may be negative itself:
+// such a call runs as a call on a dataset with a negative weight does — the f64 sum, no fold, no verdict
+// from bounds).
+inline int64_t fold_terms(const sr_dataset* ds, int64_t n_rows, int loss_code = 0) {
+  return ((ds->w && ds->w_min < 0.0) || loss_code >= kLossExprBase) ? 0 : n_rows;
+}
+// An expression loss against the dataset: the weight is its third argument exactly when the dataset has
+// weights (the reference calls loss(x, y, w) then, loss(x, y) otherwise: a MethodError for the other arity).
+inline int check_loss_expr_weights(const sr_ctx::LossExpr* e, const sr_dataset* ds) {
+  if (!e) return SR_OK;
+  if (e->p32.uses_w && !ds->w)
+    return set_error(SR_ERR_INVALID_ARG, "the loss expression references the weight, but the dataset has no weights");
+  if (!e->p32.uses_w && ds->w)
+    return set_error(SR_ERR_INVALID_ARG, "the dataset has weights, but the loss expression takes (prediction, target) only");
+  return SR_OK;
+}
 
 // ---------------------------------------------------------------- every complete tree's in-order fold
 // One loss launch of a call whose trees the in-order fold covers (sr_ctx::ref_fold): its arguments (the
@@ -728,6 +782,7 @@ struct BatchCall {
   int64_t n_eval = 0, n_rows_up = 0, nt = 0, total_nodes = 0;
   int mrb = 0, lkind = 0;  // (mrb: the row-block bound of the call's grids)
   double lparam = 0.0;
+  const sr_ctx::LossExpr* lexpr = nullptr;  // an expression-loss call's registered loss (plain LOSS calls only)
   // stage_param_table: a parametric call's table facts (nfk: the X rows a launch stages)
   const sr_param_batch* pb = nullptr;
   bool parametric = false;
@@ -796,7 +851,12 @@ struct BatchCall {
     multi = views != nullptr && gather && mode == SR_MODE_LOSS;
     n_rows_up = multi ? int64_t(views->n_views) * n_idx : n_idx;
     if (multi) allow_derived = false;
-    if (decode_loss(ctx, loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
+    // (expression losses: plain single-context LOSS calls only — the sharded, partials and parametric calls
+    //  pass no slot and are refused with the message that names the restriction)
+    const bool takes_expr = mode == SR_MODE_LOSS && !shard && ctx->param == nullptr && ctx->want_host_out;
+    if (decode_loss(ctx, loss_kind, &lkind, &lparam, takes_expr ? &lexpr : nullptr) != SR_OK) return SR_ERR_INVALID_ARG;
+    if (check_loss_expr_weights(lexpr, ds) != SR_OK) return SR_ERR_INVALID_ARG;
+    if (lexpr) allow_derived = false;  // (derived columns are chosen for the catalog builds: not measured here)
     nt = trees->n_trees;
     if (nt < 0) return set_error(SR_ERR_INVALID_ARG, "negative tree count");
     if (nt > 0 && !trees->offsets) return set_error(SR_ERR_INVALID_ARG, "sr_tree_batch has NULL arrays");
@@ -866,8 +926,11 @@ struct BatchCall {
 #endif
     // (a parametric call's kernels are a smaller set, sr_launch_eval_param: the classic kernel at its
     //  default rows per lane, 4 waves, one register-stack build per type; its knobs map onto that set)
-    R = sr_rows_per_lane<T>(mode, tier, parametric ? 0 : ctx->rows_override);
-    W = parametric ? 4 : sr_waves_per_block(int(sizeof(T)), mode, tier, R, ctx->waves_override);
+    // (an expression-loss call's likewise, sr_launch_eval_lossx: the classic kernel at its default rows per
+    //  lane, 4 waves, no register-stack build — the "rows_per_lane" / "waves" / register-stack knobs map onto it)
+    const bool small_set = parametric || lexpr != nullptr;
+    R = sr_rows_per_lane<T>(mode, tier, small_set ? 0 : ctx->rows_override);
+    W = small_set ? 4 : sr_waves_per_block(int(sizeof(T)), mode, tier, R, ctx->waves_override);
     // register-stack kernel (f32 BASIC loss over the full dataset): Rv rows per lane, used for every
     // chunk whose programs need <= 2 operand-stack slots (all trees of <= 30 nodes); other chunks run
     // the LDS-stack kernel at R rows per lane
@@ -875,6 +938,7 @@ struct BatchCall {
                ? sr_vstk_rows(int(sizeof(T)), n_eval, ctx->vstk_rows ? ctx->vstk_rows : ctx->rows_override)
                : 0;
     if (parametric && Rv > 0) Rv = sizeof(T) == 4 ? 16 : 8;  // (the one register-stack build of a parametric call)
+    if (lexpr) Rv = 0;
     // every grid of the call comes from this one spec
     gs = GridSpec{int(sizeof(T)), n_eval, W, nfk, ds->w != nullptr, ctx->tree_group, mrb};
     // a wide dataset whose register-stack tile (its rows per lane are twice the classic kernel's) would
@@ -919,7 +983,7 @@ struct BatchCall {
   // (a row-sharded call: the global rows and every shard's weights; its ranks fold or not together —
   //  the choice depends on the largest shard's rows, known to every rank)
   int plan_fold() {
-    fold_n_terms = shard ? ((ds->w && ds->shard_w_min < 0.0) ? 0 : n_total) : fold_terms(ds, n_eval);
+    fold_n_terms = shard ? ((ds->w && ds->shard_w_min < 0.0) ? 0 : n_total) : fold_terms(ds, n_eval, loss_kind);
     if (shard) ctx->fold_job.reset();
     if (ctx->want_fold && ctx->ref_fold && mode == SR_MODE_LOSS && nt > 0 && fold_n_terms > 0) {
       FoldPlanIn in;
@@ -1374,6 +1438,11 @@ struct BatchCall {
 #endif
     a.loss_kind = lkind;
     a.loss_param = T(lparam);
+    if (lexpr) {
+      const SrLossProgArgs<T> lx = lexpr->template args<T>();
+      a.lx_code = lx.code;
+      a.lx_n = lx.n;
+    }
     a.part_sum = (host_red ? ctx->h_part.as<double>() : ctx->part_sum.as<double>()) + size_t(n_rb) * size_t(t0 + p0);
     a.part_flag = (host_red ? reinterpret_cast<uint32_t*>(ctx->h_part.as<double>() + n_part)
                               : ctx->part_flag.as<uint32_t>()) + size_t(n_rb) * size_t(t0 + p0);
@@ -2605,7 +2674,7 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
     fres.debug_fail = ctx->fold_debug_fail;
   }
   finalize<T>(nt, sums.data(), flags.data(), vden[0], list.data(), int64_t(list.size()), list_ok.data(),
-              static_cast<T*>(out_loss), out_complete, fold_terms(ds, n_eval), &fold_list,
+              static_cast<T*>(out_loss), out_complete, fold_terms(ds, n_eval, loss_kind), &fold_list,
               views ? denoms.data() : nullptr, have_fold ? &fres : nullptr);
   ctx->n_ref_ok_last = fres.n_ok;
   ctx->n_ref_fail_last = fres.n_fail;
@@ -2837,7 +2906,10 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
     if (!sr_binary_grad_supported(b)) return set_error(SR_ERR_UNSUPPORTED_OP, "operator without a gradient rule");
   int lkind = 0;
   double lparam = 0.0;
-  if (decode_loss(ctx, loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
+  const sr_ctx::LossExpr* lexpr = nullptr;  // (plain trees only: the loss pass below refuses a parametric call's)
+  if (decode_loss(ctx, loss_kind, &lkind, &lparam, ctx->param == nullptr ? &lexpr : nullptr) != SR_OK) return SR_ERR_INVALID_ARG;
+  if (lexpr && !lexpr->p32.grad_ok)
+    return set_error(SR_ERR_UNSUPPORTED_OP, "the loss expression uses an operator without a gradient rule");
   int rc = eval_loss_impl<T>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete, views);
   if (rc != SR_OK) return rc;
   const int64_t nt = trees->n_trees;
@@ -3044,7 +3116,11 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
     // default's tile + stacks would not fit (many features, Float64, deep trees: ADVICE r3)
     int bdepth = 1;
     for (uint32_t t : items[b]) bdepth = std::max(bdepth, int(prog.depth[t]));
-    const int rows = parametric ? sr_grad_param_launch_rows(int(sizeof(T)), kt, int(ds->nf), ds->w != nullptr, bdepth, kWaves,
+    // (an expression-loss call: the one build per width, at the plain kernel's preferred rows per lane —
+    //  "grad_rows" maps onto it; a tile that does not fit there is an error, not another kernel)
+    const int lx_rows = sr_grad_param_rows(int(sizeof(T)), kt);
+    const bool lx_fits = sr_grad_lds_bytes(int(sizeof(T)), kt, lx_rows, int(ds->nf), ds->w != nullptr, bdepth, kWaves) <= kLdsMax;
+    const int rows = lexpr ? (lx_fits ? lx_rows : 0) : parametric ? sr_grad_param_launch_rows(int(sizeof(T)), kt, int(ds->nf), ds->w != nullptr, bdepth, kWaves,
                                                             kLdsMax, int(pC),
                                                             sr_grad_param_lane_slots(int(sizeof(T)), kt, int(pK), int(pC), ctx->grad_lane_bins != 0),
                                                             ctx->grad_rows_force)
@@ -3151,6 +3227,11 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
       const int nblk = int(lc[b].n_rb * lc[b].n_groups);
       SR_HIP_CHECK(gather ? (sr_launch_grad_param_any<T, true>(a, pa, kt, lc[b].rows, nblk, s))
                           : (sr_launch_grad_param_any<T, false>(a, pa, kt, lc[b].rows, nblk, s)));
+    } else if (lexpr) {
+      const SrLossProgArgs<T> lx = lexpr->template args<T>();
+      const int nblk = int(lc[b].n_rb * lc[b].n_groups);
+      SR_HIP_CHECK(gather ? (sr_launch_grad_lossx_any<T, true>(a, lx, kt, lc[b].rows, nblk, s))
+                          : (sr_launch_grad_lossx_any<T, false>(a, lx, kt, lc[b].rows, nblk, s)));
     } else {
       SR_HIP_CHECK(sr_launch_grad_any<T>(a, kt, gather, lc[b].rows, int(lc[b].n_rb * lc[b].n_groups), s));
     }
@@ -4125,6 +4206,10 @@ int sr_shutdown(sr_ctx* ctx) {
       b->release();
     for (HostBuf* b : {&ctx->h_prog, &ctx->h_outs, &ctx->h_grad, &ctx->h_coll, &ctx->h_part, &ctx->h_exact, &ctx->h_ptab})
       b->release();
+    for (sr_ctx::LossExpr& e : ctx->loss_exprs) {
+      if (e.dev) (void)hipFree(e.dev);
+      e.dev = nullptr;
+    }
     for (int c = 0; c < kMaxChunks; ++c) {
       (void)hipEventDestroy(ctx->ev_c0[c]);
       (void)hipEventDestroy(ctx->ev_c1[c]);
@@ -4196,6 +4281,122 @@ int sr_register_loss(sr_ctx* ctx, int kind, double param, int* loss_code) {
   ctx->losses.emplace_back(kind, param);
   *loss_code = kLossCodeBase + int(ctx->losses.size()) - 1;
   return SR_OK;
+}
+
+extern "C++" {
+namespace {
+// The operator ids of a loss expression's name lists and its one tree's bounds, checked; *key: the
+// registration's bytes (names, node fields, constants).
+int loss_expr_inputs(int n_unary, const char* const* unary_names, int n_binary, const char* const* binary_names,
+                     const sr_tree_batch* tree, SrOpset* ops, int64_t* b0, int64_t* n_nodes, std::string* key) {
+  if (n_unary < 0 || n_binary < 0 || n_unary > 255 || n_binary > 255 || (n_unary > 0 && !unary_names) ||
+      (n_binary > 0 && !binary_names))
+    return set_error(SR_ERR_INVALID_ARG, "bad operator name arrays");
+  for (int i = 0; i < n_unary; ++i) {
+    const uint32_t id = unary_names[i] ? sr_unary_id(unary_names[i]) : 0;
+    if (!id) return set_error(SR_ERR_UNSUPPORTED_OP, std::string("loss expression: unsupported unary operator: ") +
+                                                         (unary_names[i] ? unary_names[i] : "(null)"));
+    ops->unary.push_back(id);
+    if (key) key->append(unary_names[i]).push_back('\0');
+  }
+  if (key) key->push_back('|');
+  for (int i = 0; i < n_binary; ++i) {
+    const uint32_t id = binary_names[i] ? sr_binary_id(binary_names[i]) : 0;
+    if (!id) return set_error(SR_ERR_UNSUPPORTED_OP, std::string("loss expression: unsupported binary operator: ") +
+                                                         (binary_names[i] ? binary_names[i] : "(null)"));
+    ops->binary.push_back(id);
+    if (key) key->append(binary_names[i]).push_back('\0');
+  }
+  if (!tree || tree->n_trees != 1 || !tree->offsets)
+    return set_error(SR_ERR_INVALID_ARG, "a loss expression is a sr_tree_batch of exactly one tree");
+  if (!tree->degree || !tree->op || !tree->feature || !tree->constant || !tree->val)
+    return set_error(SR_ERR_INVALID_ARG, "sr_tree_batch has NULL arrays");
+  *b0 = tree->offsets[0];
+  *n_nodes = tree->offsets[1] - tree->offsets[0];
+  if (*b0 < 0 || *n_nodes < 1) return set_error(SR_ERR_INVALID_ARG, "loss expression: empty tree");
+  if (*n_nodes > SR_LX_MAX_NODES)
+    return set_error(SR_ERR_INVALID_ARG, "loss expression: " + std::to_string(*n_nodes) + " nodes; the limit is " +
+                                             std::to_string(SR_LX_MAX_NODES));
+  if (key) {
+    const size_t n = size_t(*n_nodes);
+    key->push_back('|');
+    key->append(reinterpret_cast<const char*>(tree->degree + *b0), n);
+    key->append(reinterpret_cast<const char*>(tree->op + *b0), n);
+    key->append(reinterpret_cast<const char*>(tree->constant + *b0), n);
+    key->append(reinterpret_cast<const char*>(tree->feature + *b0), n * sizeof(uint16_t));
+    key->append(reinterpret_cast<const char*>(static_cast<const double*>(tree->val) + *b0), n * sizeof(double));
+  }
+  return SR_OK;
+}
+template <typename T>
+int loss_expr_compile(const SrOpset& ops, const sr_tree_batch* tree, int64_t b0, int64_t n_nodes, SrLossProg<T>* out) {
+  std::string err;
+  if (sr_lx_compile<T>(ops.unary.data(), int(ops.unary.size()), ops.binary.data(), int(ops.binary.size()), tree->degree + b0,
+                       tree->op + b0, tree->feature + b0, tree->constant + b0, static_cast<const double*>(tree->val) + b0,
+                       n_nodes, out, &err) != 0)
+    return set_error(SR_ERR_INVALID_ARG, err);
+  return SR_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int sr_register_loss_expr(sr_ctx* ctx, int n_unary, const char* const* unary_names, int n_binary,
+                          const char* const* binary_names, const sr_tree_batch* tree, int* loss_code) {
+  if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
+  if (!loss_code) return set_error(SR_ERR_INVALID_ARG, "NULL loss_code");
+  SrOpset ops;
+  int64_t b0 = 0, n_nodes = 0;
+  std::string key;
+  int rc = loss_expr_inputs(n_unary, unary_names, n_binary, binary_names, tree, &ops, &b0, &n_nodes, &key);
+  if (rc != SR_OK) return rc;
+  Lock l(ctx);
+  for (size_t i = 0; i < ctx->loss_exprs.size(); ++i)
+    if (ctx->loss_exprs[i].key == key) {
+      *loss_code = kLossExprBase + int(i);
+      return SR_OK;
+    }
+  sr_ctx::LossExpr e;
+  if ((rc = loss_expr_compile<float>(ops, tree, b0, n_nodes, &e.p32)) != SR_OK) return rc;
+  if ((rc = loss_expr_compile<double>(ops, tree, b0, n_nodes, &e.p64)) != SR_OK) return rc;
+  e.key = std::move(key);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  void* dev = nullptr;
+  SR_HIP_CHECK(hipMalloc(&dev, sizeof(e.p32.ins) + sizeof(e.p64.ins)));
+  hipError_t he = hipMemcpy(dev, e.p32.ins, sizeof(e.p32.ins), hipMemcpyHostToDevice);
+  if (he == hipSuccess)
+    he = hipMemcpy(static_cast<char*>(dev) + sizeof(e.p32.ins), e.p64.ins, sizeof(e.p64.ins), hipMemcpyHostToDevice);
+  if (he != hipSuccess) {
+    (void)hipFree(dev);
+    return set_error(SR_ERR_HIP, std::string("loss program upload: ") + hipGetErrorString(he));
+  }
+  e.dev = dev;
+  ctx->loss_exprs.push_back(std::move(e));
+  *loss_code = kLossExprBase + int(ctx->loss_exprs.size()) - 1;
+  return SR_OK;
+}
+
+int sr_loss_expr_host(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                      const char* const* binary_names, const sr_tree_batch* tree, int64_t n, const void* pred,
+                      const void* y, const void* w, void* out_value, void* out_dvalue) {
+  if (dtype != SR_DTYPE_F32 && dtype != SR_DTYPE_F64) return set_error(SR_ERR_INVALID_ARG, "unknown dtype");
+  if (n < 0 || (n > 0 && (!pred || !y || !out_value))) return set_error(SR_ERR_INVALID_ARG, "NULL value arrays");
+  SrOpset ops;
+  int64_t b0 = 0, n_nodes = 0;
+  int rc = loss_expr_inputs(n_unary, unary_names, n_binary, binary_names, tree, &ops, &b0, &n_nodes, nullptr);
+  if (rc != SR_OK) return rc;
+  auto run = [&](auto tag) -> int {
+    using T = decltype(tag);
+    SrLossProg<T> prog;
+    const int r = loss_expr_compile<T>(ops, tree, b0, n_nodes, &prog);
+    if (r != SR_OK) return r;
+    if (prog.uses_w && !w) return set_error(SR_ERR_INVALID_ARG, "the loss expression references the weight, but w is NULL");
+    if (!prog.uses_w && w)
+      return set_error(SR_ERR_INVALID_ARG, "weights given, but the loss expression takes (prediction, target) only");
+    sr_lx_host_eval<T>(prog, n, static_cast<const T*>(pred), static_cast<const T*>(y), static_cast<const T*>(w),
+                       static_cast<T*>(out_value), static_cast<T*>(out_dvalue));
+    return SR_OK;
+  };
+  return dtype == SR_DTYPE_F32 ? run(float{}) : run(double{});
 }
 
 int sr_dataset_upload(sr_ctx* ctx, int dtype, const void* X, int64_t nfeatures, int64_t n, const void* y,
@@ -4291,6 +4492,7 @@ int check_params(const sr_dataset* ds, const sr_tree_batch* trees, const sr_para
 int sr_eval_loss_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                   const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind,
                                   void* out_loss, uint8_t* out_complete) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   int rc = validate_common(ctx, ds, opset_id, trees);
   if (rc != SR_OK) return rc;
   if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
@@ -4329,6 +4531,7 @@ int sr_eval_loss_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int o
                                         const sr_param_batch* params, const int32_t* tree_view, int n_views,
                                         const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
                                         uint8_t* out_complete) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   int rc = validate_common(ctx, ds, opset_id, trees);
   if (rc != SR_OK) return rc;
   if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
@@ -4382,6 +4585,7 @@ int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, co
 int sr_eval_grad_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                   const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind,
                                   void* out_loss, void* out_grad, uint8_t* out_complete) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   int rc = validate_common(ctx, ds, opset_id, trees);
   if (rc != SR_OK) return rc;
   if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
@@ -4400,6 +4604,7 @@ int sr_eval_grad_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int o
                                         const sr_param_batch* params, const int32_t* tree_view, int n_views,
                                         const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
                                         void* out_grad, uint8_t* out_complete) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   int rc = validate_common(ctx, ds, opset_id, trees);
   if (rc != SR_OK) return rc;
   if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
@@ -4432,6 +4637,7 @@ int sr_eval_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr
 
 int sr_eval_loss_partials(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                           int64_t n_total, int loss_kind, double* out_sum, uint32_t* out_flags, int out_on_device) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   int rc = validate_common(ctx, ds, opset_id, trees);
   if (rc != SR_OK) return rc;
   const int64_t nt = trees->n_trees;
@@ -4455,6 +4661,7 @@ int sr_eval_loss_partials(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const
 
 int sr_eval_loss_partials_packed(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                  int64_t n_total, int loss_kind, double* out, int out_on_device) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   int rc = validate_common(ctx, ds, opset_id, trees);
   if (rc != SR_OK) return rc;
   const int64_t nt = trees->n_trees;
@@ -4555,6 +4762,7 @@ int sr_comm_destroy(sr_ctx* ctx) {
 // stream, then copied to out_host (every rank gets the global sums and flag counts).
 int sr_eval_loss_partials_allreduce(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                     int64_t n_total, int loss_kind, double* out_host) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
   if (!ctx->xport) return set_error(SR_ERR_INVALID_ARG, "no communicator: call sr_comm_init first");
   int rc = validate_common(ctx, ds, opset_id, trees);
@@ -4596,6 +4804,7 @@ int sr_eval_loss_partials_allreduce(sr_ctx* ctx, const sr_dataset* ds, int opset
 
 int sr_eval_loss_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, int loss_kind,
                          void* out_loss, uint8_t* out_complete) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
   if (!ctx->xport) return set_error(SR_ERR_INVALID_ARG, "no communicator: call sr_comm_init first");
   int rc = validate_common(ctx, ds, opset_id, trees);
@@ -4611,6 +4820,7 @@ int sr_eval_loss_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const 
 
 int sr_eval_loss_tree_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                               int loss_kind, void* out_loss, uint8_t* out_complete) {
+  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
   if (!ctx->xport) return set_error(SR_ERR_INVALID_ARG, "no communicator: call sr_comm_init first");
   int rc = validate_common(ctx, ds, opset_id, trees);

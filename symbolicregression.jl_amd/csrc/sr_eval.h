@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sr_ops.h"
+#include "sr_loss_expr.h"  // the expression-loss program and its interpreters (HIP-free)
 #include "sr_plan.h"  // modes, tiers, SrSegment, SrDerivedSpec, the launch-shape functions (HIP-free)
 #include "../../include/sr_amd.h"
 
@@ -182,6 +183,11 @@ struct SrEvalArgs {
   double* fold_est_sum;
   uint32_t* fold_est_cnt;
   uint32_t fold_est_min;
+  // SR_LOSS_EXPR loss builds (sr_inst_*lossx*.hip; last again, no other kernel reads them): the loss
+  // program (sr_loss_expr.h) in a device buffer of the context — not in the argument block, which is host
+  // memory here — read with wave-uniform loads, and its length
+  const SrIns<T>* lx_code;
+  int lx_n;
 };
 // A parametric call's table: ptab[tree * p_stride + k * n_classes + class] at the caller's tree index (as
 // `offsets`).  The rows' 0-based classes are the last staged X row (the dataset's hidden row:
@@ -216,6 +222,14 @@ hipError_t sr_launch_loss_cand(const SrEvalArgs<T>& a, int R, int waves, int n_b
 template <typename T>
 hipError_t sr_launch_eval_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int mode, bool gather, int tier, int R,
                                 int waves, bool vstk, int n_blocks, hipStream_t s);
+// The loss launches of an expression-loss call (a.loss_kind == SR_LOSS_EXPR; sr_inst_*lossx*.hip): the
+// classic kernel at its default rows per lane — Float32 BASIC 8 / FULL 4, Float64 4 / 2 — full view or
+// gathered, 4 waves; hipErrorInvalidValue for any other shape or a missing program (the host maps such a
+// call's knobs onto this set: sr_capi.cpp choose_kernels).  sr_launch_eval routes LOSS launches of such
+// arguments here itself: no generic-loss kernel, whose default case is L2, ever runs them.
+template <typename T>
+hipError_t sr_launch_eval_lossx(const SrEvalArgs<T>& a, bool gather, int tier, int R, int waves, bool vstk, int n_blocks,
+                                hipStream_t s);
 template <typename T>
 hipError_t sr_launch_derived(const T* X, int64_t ld, const int64_t* row_idx, int64_t n_view, int64_t n_pad,
                              const SrDerivedSpec& spec, T* out, int64_t dld, hipStream_t s);
@@ -363,6 +377,12 @@ inline int sr_grad_param_launch_rows(int elem_size, int kt, int nf, bool weighte
 }
 template <typename T, bool GATHER>
 hipError_t sr_launch_grad_param_any(const SrGradArgs<T>& a, const SrGradParamArgs<T>& p, int kt, int rows, int n_blocks,
+                                    hipStream_t s);
+// The expression-loss build of the gradient kernel (sr_grad_lossx_kernel, sr_grad_lossx_*.hip): d loss / d
+// pred from the loss program, the weight handed to it.  One build per tangent width, at sr_grad_param_rows
+// rows per lane (the plain kernel's preferred count); hipErrorInvalidValue for any other.
+template <typename T, bool GATHER>
+hipError_t sr_launch_grad_lossx_any(const SrGradArgs<T>& a, const SrLossProgArgs<T>& x, int kt, int rows, int n_blocks,
                                     hipStream_t s);
 // The reference's loss fold in row order for listed trees (sr_fold.h; sr_aux.hip): predictions
 // pred[b][pred_ld] of n rows, losses against y (and w) at row_idx (or the row itself).

@@ -1,6 +1,6 @@
 // sr_grad_body.h — the body of the gradient kernels, included (as text, inside the kernel's braces) by
-// sr_grad_impl.h: once with SR_GRAD_PARAM 0 for sr_grad_kernel(a) and once with SR_GRAD_PARAM 1 for
-// sr_grad_param_kernel(a, p).  A textual include and not a shared inlined function: the plain kernels
+// sr_grad_impl.h: once with SR_GRAD_PARAM 0 for sr_grad_kernel(a), once with SR_GRAD_PARAM 1 for
+// sr_grad_param_kernel(a, p), and once with SR_GRAD_LOSSX 1 for sr_grad_lossx_kernel(a, x).  A textual include and not a shared inlined function: the plain kernels
 // then compile from exactly the text they always had (a force-inlined shared body moved their register
 // counts; tools/kernel_resources.py compares them with the parent's).
   // rows per lane: lane + 64 j, j < R; a staged tile of TROWS rows is interpreted in TROWS / ROWS
@@ -479,6 +479,22 @@
     }
     // d loss / d constant: (d loss / d pred) * d pred / d constant, padded rows excluded
     T coefs[R];
+#if SR_GRAD_LOSSX
+    {
+      // an expression loss: d value / d pred from the loss program, one pass over the lane's R rows; the
+      // weight is the program's third argument (no coef *= w below)
+      SrLxVec<T, R> pv, yv, wv;
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        pv[j] = v[j];
+        yv[j] = ys[ro + j * 64 + lane];
+        wv[j] = weighted ? wsv[ro + j * 64 + lane] : T(1);
+      }
+      pv = sr_lx_deriv<T, R, SrLxDevOps<T, R>>(lx.code, lx.n, pv, yv, wv);
+#pragma unroll
+      for (int j = 0; j < R; ++j) coefs[j] = pv[j];
+    }
+#else
     if (a.loss_kind == SR_LOSS_L2) {
 #pragma unroll
       for (int j = 0; j < R; ++j) coefs[j] = sr_elem_loss_deriv<T>(SR_LOSS_L2, v[j], ys[ro + j * 64 + lane], T(0));
@@ -493,11 +509,14 @@
 #pragma unroll
       for (int j = 0; j < R; ++j) coefs[j] = pv[j];
     }
+#endif
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       const int r = j * 64 + lane;
       T coef = coefs[j];
+#if !SR_GRAD_LOSSX
       if (weighted) coef *= wsv[ro + r];
+#endif
       if (row0 + r >= a.n_rows) coef = T(0);
 #pragma unroll
       for (int q = 0; q < KT; ++q) acc[q] = __builtin_fma(double(coef), double(dv[j][q]), acc[q]);

@@ -119,16 +119,32 @@ constexpr uint32_t SR_GV_PL = 100u, SR_GV_PR = 101u;
 // by the wave into its LDS bin [tangent][class]; the bins go out per row block and the row blocks are
 // reduced in order (sr_launch_grad_reduce).  No atomics: the same bits run to run, for every R and
 // whatever else is in the launch.
+//
+// LOSSX (sr_grad_lossx_kernel, expression losses; sr_grad_lossx_*.hip): only the per-row coefficient differs —
+// d value / d pred from the call's loss program by forward mode (sr_loss_expr.h), the weight handed to the
+// program and not multiplied in afterwards.
 template <typename T, int KT, int W, bool GATHER, int R>
 __global__ void __launch_bounds__(W * 64) sr_grad_kernel(const SrGradArgs<T> a) {
 #define SR_GRAD_PARAM 0
+#define SR_GRAD_LOSSX 0
 #include "sr_grad_body.h"
+#undef SR_GRAD_LOSSX
 #undef SR_GRAD_PARAM
 }
 template <typename T, int KT, int W, bool GATHER, int R>
 __global__ void __launch_bounds__(W * 64) sr_grad_param_kernel(const SrGradArgs<T> a, const SrGradParamArgs<T> p) {
 #define SR_GRAD_PARAM 1
+#define SR_GRAD_LOSSX 0
 #include "sr_grad_body.h"
+#undef SR_GRAD_LOSSX
+#undef SR_GRAD_PARAM
+}
+template <typename T, int KT, int W, bool GATHER, int R>
+__global__ void __launch_bounds__(W * 64) sr_grad_lossx_kernel(const SrGradArgs<T> a, const SrLossProgArgs<T> lx) {
+#define SR_GRAD_PARAM 0
+#define SR_GRAD_LOSSX 1
+#include "sr_grad_body.h"
+#undef SR_GRAD_LOSSX
 #undef SR_GRAD_PARAM
 }
 
@@ -189,8 +205,41 @@ hipError_t sr_launch_grad_param_any(const SrGradArgs<T>& a, const SrGradParamArg
   }
 }
 
+// The expression-loss builds: one per tangent width, at sr_grad_param_rows rows per lane.
+template <typename T, int KT, int W, bool GATHER, int R>
+hipError_t sr_launch_grad_lossx(const SrGradArgs<T>& a, const SrLossProgArgs<T>& x, int n_blocks, hipStream_t s) {
+  if (x.code == nullptr || x.n < 1 || x.n > SR_LX_MAX_INS || a.loss_kind != SR_LOSS_EXPR) return hipErrorInvalidValue;
+  const size_t lds = sr_grad_lds_bytes(int(sizeof(T)), KT, R, a.nf, a.w != nullptr, a.stack_depth, W);
+  const void* fn = reinterpret_cast<const void*>(&sr_grad_lossx_kernel<T, KT, W, GATHER, R>);
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((sr_grad_lossx_kernel<T, KT, W, GATHER, R>), dim3(n_blocks), dim3(W * 64), lds, s, a, x);
+  return hipGetLastError();
+}
+template <typename T, bool GATHER>
+hipError_t sr_launch_grad_lossx_any(const SrGradArgs<T>& a, const SrLossProgArgs<T>& x, int kt, int rows, int n_blocks,
+                                    hipStream_t s) {
+  auto go = [&](auto ktc) -> hipError_t {
+    constexpr int KT = decltype(ktc)::value;
+    constexpr int RR = sr_grad_param_rows(int(sizeof(T)), KT);
+    if (rows != RR) return hipErrorInvalidValue;
+    return sr_launch_grad_lossx<T, KT, 4, GATHER, RR>(a, x, n_blocks, s);
+  };
+  switch (kt) {
+    case 1: return go(std::integral_constant<int, 1>{});
+    case 2: return go(std::integral_constant<int, 2>{});
+    case 4: return go(std::integral_constant<int, 4>{});
+    case 8: return go(std::integral_constant<int, 8>{});
+    case 16: return go(std::integral_constant<int, 16>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
 template <typename T>
 hipError_t sr_launch_grad_any(const SrGradArgs<T>& a, int kt, bool gather, int rows, int n_blocks, hipStream_t s) {
+  if (a.loss_kind == SR_LOSS_EXPR) return hipErrorInvalidValue;  // (sr_launch_grad_lossx_any: never sr_elem_loss_deriv's default case)
   auto go = [&](auto g) -> hipError_t {
     constexpr bool G = decltype(g)::value;
     switch (kt) {

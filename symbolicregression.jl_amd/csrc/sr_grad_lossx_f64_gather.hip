@@ -1,0 +1,6 @@
+// sr_grad_lossx_f64_gather.hip — the expression-loss gradient kernels (sr_grad_impl.h, LOSSX), double, gathered rows (row views):
+// tangent widths 1 - 16 at sr_grad_param_rows rows per lane.
+#include "sr_grad_impl.h"
+
+template hipError_t sr_launch_grad_lossx_any<double, true>(const SrGradArgs<double>&, const SrLossProgArgs<double>&, int, int, int,
+                                                          hipStream_t);

@@ -67,9 +67,13 @@ enum SrLossKind : int32_t {
   SR_LOSS_EXP = 16,            // ExpLoss: exp(-a)
   SR_LOSS_SIGMOID = 17,        // SigmoidLoss: 1 - tanh(a)
   SR_LOSS_DWD_MARGIN = 18,     // DWDMarginLoss(q): a <= q/(q+1) ? 1 - a : (q^q/(q+1)^(q+1)) / a^q
-  SR_LOSS_COUNT
+  SR_LOSS_COUNT,
+  // a loss given as an expression over (prediction, target, weight): sr_loss_expr.h.  After the catalog:
+  // sr_register_loss takes catalog kinds only, sr_register_loss_expr hands out the codes that decode to this
+  SR_LOSS_EXPR = SR_LOSS_COUNT
 };
 // Losses whose value is NaN whenever the prediction is (the deferred NaN test may read the loss sum)
+// (never an expression loss: what it does with a NaN is the expression's business)
 SR_HD inline bool sr_loss_propagates_nan(int32_t kind) {
   return kind == SR_LOSS_L2 || kind == SR_LOSS_L1 || kind == SR_LOSS_LP || kind == SR_LOSS_LOGIT ||
          kind == SR_LOSS_HUBER || kind == SR_LOSS_L2_MARGIN || kind == SR_LOSS_EXP || kind == SR_LOSS_SIGMOID;

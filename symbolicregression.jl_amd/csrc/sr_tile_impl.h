@@ -97,6 +97,24 @@ struct SrMinWavesFor {
                                                                 : SrMinWaves<W>::value;
 };
 
+// An expression-loss build (LK == SR_LOSS_EXPR) starts from its generic-loss sibling's bound; the two
+// BASIC-tier ones give up one wave per SIMD (Float32 8 rows: 5 -> 4, 128 VGPRs; Float64 4 rows: 4 -> 3,
+// 168): the loss interpreter keeps four live R-vectors and its three arguments across its row callees,
+// which at the sibling's budget spilled (81 / 56 VGPRs against 21 / 8) around every loss instruction.
+#ifndef SR_MIN_WAVES_LOSSX_F32
+#define SR_MIN_WAVES_LOSSX_F32 4
+#endif
+#ifndef SR_MIN_WAVES_LOSSX_F64
+#define SR_MIN_WAVES_LOSSX_F64 3
+#endif
+template <typename T, int R, int TIER, int W, bool VSTK, int LK, bool GATHER, int MODE>
+struct SrMinWavesKernel {
+  static constexpr bool lossx = LK == SR_LOSS_EXPR;
+  static constexpr int value = (lossx && TIER == SR_TIER_BASIC && sizeof(T) == 4 && R == 8)   ? SR_MIN_WAVES_LOSSX_F32
+                               : (lossx && TIER == SR_TIER_BASIC && sizeof(T) == 8 && R == 4) ? SR_MIN_WAVES_LOSSX_F64
+                                   : SrMinWavesFor<T, R, TIER, W, VSTK, (lossx ? -1 : LK), GATHER, MODE>::value;
+};
+
 // 16-byte chunks of C values.
 template <typename T>
 struct SrChunk;
@@ -843,14 +861,15 @@ __device__ __forceinline__ typename SrWindow<T>::type sr_window_lds(const uint4*
 // the waves of a block get equal work).  Wave w owns positions tree0 + w + W*j ("slot" j, j < 64);
 // everything per tree lives in that wave: program bounds in lane j's VGPRs, the loss accumulator in
 // lane j, the non-finite / suspicious bits in scalar masks.
-// LK: elementwise loss fixed at compile time (SR_LOSS_L2 / SR_LOSS_L1), or -1 = a.loss_kind.
+// LK: elementwise loss fixed at compile time (SR_LOSS_L2 / SR_LOSS_L1), or -1 = a.loss_kind; SR_LOSS_EXPR: the
+// LOSS epilogue interprets the call's loss program (a.lx_code; sr_loss_expr.h) instead of sr_elem_loss.
 // VSTK: the operand stack (<= 2 slots: every tree of <= 30 nodes) lives in VGPRs.
 // TIERP: the operator tier (SR_TIER_BASIC / SR_TIER_FULL), | SR_TIER_PARAM for the builds of parametric
 // calls (ParametricExpression batches), which alone implement LOAD_PARAM and the P binary operands
 // (sr_ops.h).  A flag on this parameter, not a parameter of its own: the kernels of plain calls keep
 // their symbol names and — the new cases are empty in them — their code.
 template <typename T, int R, int MODE, bool GATHER, int TIERP, int W, int LK, bool VSTK>
-__global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_FULL), W, VSTK, LK, GATHER, MODE>::value)) sr_tile_kernel(const SrEvalArgs<T> a) {
+__global__ void __launch_bounds__(W * 64, (SrMinWavesKernel<T, R, (TIERP & SR_TIER_FULL), W, VSTK, LK, GATHER, MODE>::value)) sr_tile_kernel(const SrEvalArgs<T> a) {
   constexpr int TIER = TIERP & SR_TIER_FULL;
   constexpr bool PARAM = (TIERP & SR_TIER_PARAM) != 0;
   // the loss launch of a large call under the in-order fold: each row block's composed steps under
@@ -1425,7 +1444,24 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
             T l[R];
             T yv[R];
             L::load(y_lane, yv);
-            if (weighted) {
+            if constexpr (LK == SR_LOSS_EXPR) {
+              // an expression loss (sr_loss_expr.h): the program, in device memory, runs once over the
+              // lane's R rows — one dispatch per loss instruction, uniform control flow.  The weight is the
+              // expression's third argument and is NOT multiplied in afterwards: the reference calls
+              // loss(x[i], y[i], w[i]) and divides by sum(w) (src/LossFunctions.jl:38-58)
+              SrLxVec<T, R> pv, tv, wv;
+              T wl[R];
+              if (weighted) L::load(w_lane, wl);
+#pragma unroll
+              for (int r = 0; r < R; ++r) {
+                pv[r] = tos[r];
+                tv[r] = yv[r];
+                wv[r] = weighted ? wl[r] : T(1);
+              }
+              const SrLxVec<T, R> lv = sr_lx_value<T, R, SrLxDevOps<T, R>>(a.lx_code, a.lx_n, pv, tv, wv);
+#pragma unroll
+              for (int r = 0; r < R; ++r) l[r] = lv[r];
+            } else if (weighted) {
               T wv[R];
               L::load(w_lane, wv);
 #pragma unroll
@@ -1508,7 +1544,9 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesFor<T, R, (TIERP & SR_TIER_
               // The tile's T sum of the losses is +Inf (rare; s is wave-uniform): SR_FLAG_ELEMINF when
               // a loss or a pair sum is +Inf (the reference's fold is then +Inf); otherwise only the
               // longer sums overflowed and the host decides the fold (sr_fold.h)
-              if (!(s <= SrM<T>::big) && sr_ballot(pair_max == T(INFINITY))) emask |= bit;
+              // (an expression loss may be negative: no verdict from the pair sums, the f64 sum decides)
+              if constexpr (LK == SR_LOSS_EXPR) {
+              } else if (!(s <= SrM<T>::big) && sr_ballot(pair_max == T(INFINITY))) emask |= bit;
               if constexpr (CAND) {
                 // The in-order fold's steps of this tile under SR_FCAND_N candidate binades (the FOLD pass's
                 // fast path, sr_fold_tile_fast_n: the same pairs bit for bit), so that the plan can take the

@@ -312,8 +312,51 @@ loss_spec(l::LF.SigmoidLoss) = (17, 0.0)
 loss_spec(l::LF.DWDMarginLoss) = (18, Float64(l.q))
 loss_spec(l) = nothing  # any other elementwise loss (or a custom function) stays on the CPU path
 
+# ---------------------------------------------------------------- expression losses
+# (written, not executed: no Julia runtime in the build image; the Python mirror's Context.loss_code makes
+#  the same call and is what the tests run)
+"""
+    register_expression_loss(ctx, ex) -> Cint
+
+An elementwise loss the device can run in place of a closure `(x, y) -> ...` / `(x, y, w) -> ...`
+(src/LossFunctions.jl:38-58): `ex` is an `Expression` over `x1` (prediction), `x2` (target) and `x3`
+(weight) whose operators are in the device catalog, e.g.
+`parse_expression(:(log(cosh(x1 - x2))); operators, variable_names=["x1", "x2", "x3"])`.  Registered once per
+context (`sr_register_loss_expr`); the code is what the scoring calls take as `loss_kind` for plain trees.
+Constants go up as Float64 and are rounded to the dataset's element type on the device side.  `nothing` when
+an operator is outside the catalog (the caller keeps the CPU path).
+"""
+function register_expression_loss(ctx::DeviceContext, ex::AbstractExpression)
+    operators = get_operators(ex, nothing)
+    un = [string(nameof(f)) for f in operators.unaops]
+    bi = [string(nameof(f)) for f in operators.binops]
+    f = flatten([ex], Float64)
+    code = Ref{Cint}(0)
+    lock(ctx.lock) do
+        GC.@preserve f begin
+            b = SrTreeBatch(1, pointer(f.offsets), pointer(f.degree), pointer(f.op), pointer(f.feature),
+                            pointer(f.constant), Ptr{Cvoid}(pointer(f.val)))
+            rc = ccall((:sr_register_loss_expr, LIB), Cint,
+                       (Ptr{Cvoid}, Cint, Ptr{Cstring}, Cint, Ptr{Cstring}, Ref{SrTreeBatch}, Ref{Cint}),
+                       ctx.handle, length(un), un, length(bi), bi, b, code)
+            rc == SR_ERR_UNSUPPORTED_OP && return nothing
+            check(rc)
+            code[]
+        end
+    end
+end
+
 const LOSS_CODES = Dict{Tuple{Ptr{Cvoid},Int,Float64},Cint}()
+const LOSS_EXPR_CODES = Dict{Tuple{Ptr{Cvoid},UInt},Union{Nothing,Cint}}()
 function loss_kind(options)
+    # `elementwise_loss` given as an Expression over x1, x2, x3 (MI355XOptions accepts one in place of the
+    # closure it stands for): registered once per (context, expression)
+    if options.elementwise_loss isa AbstractExpression
+        ctx = context()
+        return get!(LOSS_EXPR_CODES, (ctx.handle, hash(options.elementwise_loss))) do
+            register_expression_loss(ctx, options.elementwise_loss)
+        end
+    end
     spec = loss_spec(options.elementwise_loss)
     spec === nothing && return nothing
     kind, param = spec

@@ -40,7 +40,7 @@ from .node import (
     string_tree,
 )
 from .operators import OperatorEnum
-from .options import Options, ParametricExpressionSpec
+from .options import LossExpression, Options, ParametricExpressionSpec
 from .search import HallOfFame, PopMember, SearchOptions, equation_search
 
 __all__ = [

@@ -101,6 +101,8 @@ EXPORTED_SYMBOLS = (
     "sr_eval_grad_batch_parametric",
     "sr_eval_grad_batch_views_parametric",
     "sr_optimize_constants_batch_parametric",
+    "sr_register_loss_expr",
+    "sr_loss_expr_host",
 )
 
 # mutation kinds in sr_search_options.mutation_weights order (SR_MUT_*)
@@ -198,6 +200,14 @@ def _load():
             [P, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(c_int)],
         ),
         "sr_register_loss": (c_int, [P, c_int, c_double, POINTER(c_int)]),
+        "sr_register_loss_expr": (
+            c_int,
+            [P, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), POINTER(c_int)],
+        ),
+        "sr_loss_expr_host": (
+            c_int,
+            [c_int, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), c_int64, P, P, P, P, P],
+        ),
         "sr_dataset_upload": (c_int, [P, c_int, P, c_int64, c_int64, P, P, POINTER(P)]),
         "sr_dataset_upload_classes": (c_int, [P, c_int, P, c_int64, c_int64, P, P, P, ctypes.c_int32, POINTER(P)]),
         "sr_dataset_free": (c_int, [P]),

@@ -41,6 +41,20 @@ class DeviceContext:
         """The `loss_kind` the C ABI takes for options' elementwise loss: the kind itself for the
         parameter-free losses (and HuberLoss(1)), else the code sr_register_loss returns."""
         kind, param = options.loss_kind, float(getattr(options, "loss_param", 0.0))
+        expr = getattr(options, "loss_expression", None)
+        if expr is not None:  # an expression loss: registered once per (context, expression)
+            codes = self.__dict__.setdefault("_loss_expr_codes", {})
+            key = expr.key()
+            if key not in codes:
+                ops, b = expr.operators, expr.batch()
+                un = (ctypes.c_char_p * max(1, len(ops.unaops)))(*[s.encode() for s in ops.unaops])
+                bi = (ctypes.c_char_p * max(1, len(ops.binops)))(*[s.encode() for s in ops.binops])
+                ts = b.to_struct()
+                out = ctypes.c_int()
+                _lib.check(_lib.lib.sr_register_loss_expr(self.handle, len(ops.unaops), un, len(ops.binops), bi,
+                                                          ctypes.byref(ts), ctypes.byref(out)))
+                codes[key] = int(out.value)
+            return codes[key]
         if kind in (0, 1, 3, 9, 10, 11, 12, 14, 15, 16, 17) or (kind == 4 and param == 1.0):
             return kind
         key = (kind, param)

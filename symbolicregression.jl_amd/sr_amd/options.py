@@ -9,11 +9,12 @@ src/OptionsStruct.jl:186-187).
 """
 from __future__ import annotations
 
+import ast
 import re
 
 import numpy as np
 
-from .operators import OperatorEnum
+from .operators import BINARY_ALIASES, UNARY_ALIASES, OperatorEnum
 
 # Elementwise losses the device evaluates: the LossFunctions.jl catalog src/Options.jl:301-328 lists,
 # as (SrLossKind, parameter name or None).  Kinds match include/sr_amd.h SR_LOSS_*.
@@ -50,6 +51,101 @@ def parse_loss(spec):
             raise ValueError(f"{name} needs its parameter {pname}, e.g. {name}(1.0)")
         return kind, LOSS_DEFAULTS[name]
     return kind, float(arg)
+
+
+# An elementwise loss given as an expression (include/sr_amd.h sr_register_loss_expr): SrLossKind's
+# SR_LOSS_EXPR, after the catalog.
+LOSS_KIND_EXPR = 19
+# The expression's operators: the whole device catalog, whatever the search's own operator set is.
+LOSS_OPERATORS = OperatorEnum(sorted(set(UNARY_ALIASES.values())), sorted(set(BINARY_ALIASES.values())))
+_LOSS_FORMS = (
+    re.compile(r"\s*[A-Za-z_]\w*\s*\(([^()]*)\)\s*=(?!=)(.+)", re.S),  # loss(pred, target[, weight]) = BODY
+    re.compile(r"\s*\(([^()]*)\)\s*->(.+)", re.S),                     # (pred, target[, weight]) -> BODY
+)
+
+
+class LossExpression:
+    """``"loss(prediction, target) = BODY"`` or ``"(prediction, target) -> BODY"``, with two or three
+    argument names of the user's choice (the third is the weight) — the forms SymbolicRegression.jl
+    (``elementwise_loss = (x, y) -> ...``, src/LossFunctions.jl:38-58) and PySR users write.  ``BODY`` is an
+    expression over those names, numbers and the operators of the device catalog (``LOSS_OPERATORS``); it is
+    parsed by ``parse_expression`` into ``tree``, whose leaves are feature 1 = prediction, 2 = target,
+    3 = weight.  ``ValueError`` for an unknown name or operator and for fewer than two or more than three
+    arguments.  The device evaluates it in the dataset's element type (constants rounded to it)."""
+
+    def __init__(self, spec: str):
+        from .node import parse_expression
+
+        m = next((m for m in (f.fullmatch(spec) for f in _LOSS_FORMS) if m), None)
+        if m is None:
+            raise ValueError(f"elementwise_loss {spec!r}: expected 'loss(prediction, target) = BODY' or "
+                             "'(prediction, target) -> BODY'")
+        names = [a.strip() for a in m.group(1).split(",")]
+        if not 2 <= len(names) <= 3:
+            raise ValueError(f"elementwise_loss {spec!r}: a loss takes (prediction, target) or (prediction, target, "
+                             f"weight), got {len(names)} arguments")
+        if any(not n.isidentifier() for n in names) or len(set(names)) != len(names):
+            raise ValueError(f"elementwise_loss {spec!r}: bad argument names {names}")
+        try:
+            body = ast.parse(m.group(2).strip().replace("^", "**"), mode="eval")
+        except SyntaxError as e:
+            raise ValueError(f"elementwise_loss {spec!r}: cannot parse the body ({e.msg})") from None
+        called = {id(c.func) for c in ast.walk(body) if isinstance(c, ast.Call)}
+        for n in ast.walk(body):
+            if isinstance(n, ast.Name) and id(n) not in called:
+                if n.id in names:
+                    n.id = f"x{names.index(n.id) + 1}"
+                elif n.id not in ("inf", "Inf", "nan", "NaN"):
+                    raise ValueError(f"elementwise_loss {spec!r}: unknown name {n.id!r} (arguments: {names})")
+        try:
+            self.tree = parse_expression(ast.unparse(body), LOSS_OPERATORS)
+        except ValueError as e:
+            raise ValueError(f"elementwise_loss {spec!r}: {e}") from None
+        except (AttributeError, KeyError) as e:
+            raise ValueError(f"elementwise_loss {spec!r}: cannot parse the body ({e!r})") from None
+        self.spec = spec
+        self.n_args = len(names)
+        self.operators = LOSS_OPERATORS
+
+    def batch(self):
+        """The tree as a one-tree TreeBatch with Float64 constants (what sr_register_loss_expr takes)."""
+        from .node import flatten_trees
+
+        return flatten_trees([self.tree], np.float64)
+
+    def key(self):
+        b = self.batch()
+        return (b.degree.tobytes(), b.op.tobytes(), b.feature.tobytes(), b.constant.tobytes(), b.val.tobytes())
+
+    def host_eval(self, prediction, target, weight=None, deriv=False):
+        """The library's host interpreter (sr_loss_expr_host: the compiler and interpreter the kernels run,
+        no device needed) on arrays of one dtype (Float32 / Float64): L(prediction, target, weight), and with
+        ``deriv`` also d L / d prediction by forward mode."""
+        import ctypes
+
+        from . import _lib
+
+        p = np.ascontiguousarray(prediction)
+        if p.dtype not in (np.float32, np.float64):
+            raise ValueError("host_eval takes Float32 or Float64 arrays")
+        t = np.ascontiguousarray(target, dtype=p.dtype)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=p.dtype)
+        if t.shape != p.shape or (w is not None and w.shape != p.shape):
+            raise ValueError("prediction, target and weight must have one shape")
+        ops, b = self.operators, self.batch()
+        un = (ctypes.c_char_p * max(1, len(ops.unaops)))(*[s.encode() for s in ops.unaops])
+        bi = (ctypes.c_char_p * max(1, len(ops.binops)))(*[s.encode() for s in ops.binops])
+        ts = b.to_struct()
+        out = np.empty_like(p)
+        dout = np.empty_like(p) if deriv else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        _lib.check(_lib.lib.sr_loss_expr_host(_lib.SR_DTYPE_F32 if p.dtype == np.float32 else _lib.SR_DTYPE_F64,
+                                              len(ops.unaops), un, len(ops.binops), bi, ctypes.byref(ts), p.size,
+                                              ptr(p), ptr(t), ptr(w), ptr(out), ptr(dout)))
+        return (out, dout) if deriv else out
+
+    def __repr__(self):
+        return f"LossExpression({self.spec!r})"
 
 
 class ParametricExpressionSpec:
@@ -102,7 +198,14 @@ class Options:
         if callable(elementwise_loss) and not isinstance(elementwise_loss, str):
             raise ValueError("custom elementwise loss functions stay on the reference CPU path")
         self.elementwise_loss = elementwise_loss
-        self.loss_kind, self.loss_param = parse_loss(elementwise_loss)
+        # "loss(pred, target) = BODY" / "(pred, target) -> BODY": an expression loss (its tree is kept here;
+        # Context.loss_code registers it once per context); any other string is a catalog loss, as before
+        self.loss_expression = None
+        if isinstance(elementwise_loss, str) and ("=" in elementwise_loss or "->" in elementwise_loss):
+            self.loss_expression = LossExpression(elementwise_loss)
+            self.loss_kind, self.loss_param = LOSS_KIND_EXPR, 0.0
+        else:
+            self.loss_kind, self.loss_param = parse_loss(elementwise_loss)
         self.loss_function = loss_function
         self.loss_function_expression = loss_function_expression
         self.parsimony = np.float32(parsimony)
