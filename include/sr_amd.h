@@ -398,6 +398,19 @@ int sr_compile_info_parametric(int dtype, int n_unary, const char* const* unary_
                                uint8_t* out_static_bad, int32_t* out_max_depth, void* out_code,
                                int64_t code_capacity);
 
+/* The same dry runs for the GRADIENT programs sr_eval_grad_batch (and its parametric sibling) compile: constants
+ * stay live (no folding), no pair, post-unary or post-constant fusion, and every constant operand carries its
+ * pre-order slot (the tangent it seeds) in the instruction's operand index.  Same arguments and outputs. */
+int sr_compile_info_grad(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                         const char* const* binary_names, const sr_tree_batch* trees, int64_t n_rows,
+                         int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
+                         void* out_code, int64_t code_capacity);
+int sr_compile_info_grad_parametric(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                                    const char* const* binary_names, const sr_tree_batch* trees,
+                                    const sr_param_batch* params, int64_t n_rows, int64_t nfeatures,
+                                    int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
+                                    void* out_code, int64_t code_capacity);
+
 /*
  * Host-side evaluation of one unary operator (the code constant folding uses; the device runs the
  * same functions): out[i] = op(x[i]) for n values of dtype.  For testing host/device agreement.

@@ -4984,7 +4984,7 @@ int sr_eval_grad_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr
 static int compile_info_impl(int dtype, int n_unary, const char* const* unary_names, int n_binary,
                              const char* const* binary_names, const sr_tree_batch* trees, const SrParamNodes* pn,
                              int64_t n_rows, int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad,
-                             int32_t* out_max_depth, void* out_code, int64_t code_capacity) {
+                             int32_t* out_max_depth, void* out_code, int64_t code_capacity, bool grad = false) {
   if (!trees || n_unary < 0 || n_binary < 0 || (n_unary > 0 && !unary_names) || (n_binary > 0 && !binary_names))
     return set_error(SR_ERR_INVALID_ARG, "bad arguments");
   SrOpset o;
@@ -5016,13 +5016,13 @@ static int compile_info_impl(int dtype, int n_unary, const char* const* unary_na
   };
   if (dtype == SR_DTYPE_F32) {
     SrProgramBatch<float> prog;
-    int rc = sr_compile_batch<float>(*trees, o, n_rows, nfeatures, false, &prog, &err, nullptr, pn);
+    int rc = sr_compile_batch<float>(*trees, o, n_rows, nfeatures, grad, &prog, &err, nullptr, pn);
     if (rc != SR_OK) return set_error(rc, err);
     return report(prog);
   }
   if (dtype == SR_DTYPE_F64) {
     SrProgramBatch<double> prog;
-    int rc = sr_compile_batch<double>(*trees, o, n_rows, nfeatures, false, &prog, &err, nullptr, pn);
+    int rc = sr_compile_batch<double>(*trees, o, n_rows, nfeatures, grad, &prog, &err, nullptr, pn);
     if (rc != SR_OK) return set_error(rc, err);
     return report(prog);
   }
@@ -5047,6 +5047,26 @@ int sr_compile_info_parametric(int dtype, int n_unary, const char* const* unary_
   const SrParamNodes pn{params->is_parameter, params->parameter, params->max_parameters};
   return compile_info_impl(dtype, n_unary, unary_names, n_binary, binary_names, trees, &pn, n_rows, nfeatures, out_len,
                            out_static_bad, out_max_depth, out_code, code_capacity);
+}
+
+int sr_compile_info_grad(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                         const char* const* binary_names, const sr_tree_batch* trees, int64_t n_rows,
+                         int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
+                         void* out_code, int64_t code_capacity) {
+  return compile_info_impl(dtype, n_unary, unary_names, n_binary, binary_names, trees, nullptr, n_rows, nfeatures,
+                           out_len, out_static_bad, out_max_depth, out_code, code_capacity, true);
+}
+
+int sr_compile_info_grad_parametric(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                                    const char* const* binary_names, const sr_tree_batch* trees,
+                                    const sr_param_batch* params, int64_t n_rows, int64_t nfeatures,
+                                    int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
+                                    void* out_code, int64_t code_capacity) {
+  if (!params) return set_error(SR_ERR_INVALID_ARG, "NULL parameter batch");
+  if (params->max_parameters < 0 || params->max_parameters > 65535) return set_error(SR_ERR_INVALID_ARG, "bad max_parameters");
+  const SrParamNodes pn{params->is_parameter, params->parameter, params->max_parameters};
+  return compile_info_impl(dtype, n_unary, unary_names, n_binary, binary_names, trees, &pn, n_rows, nfeatures, out_len,
+                           out_static_bad, out_max_depth, out_code, code_capacity, true);
 }
 
 int sr_host_unary(int dtype, const char* name, int64_t n, const void* x, void* out) {

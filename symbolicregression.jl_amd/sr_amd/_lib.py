@@ -103,6 +103,8 @@ EXPORTED_SYMBOLS = (
     "sr_optimize_constants_batch_parametric",
     "sr_register_loss_expr",
     "sr_loss_expr_host",
+    "sr_compile_info_grad",
+    "sr_compile_info_grad_parametric",
 )
 
 # mutation kinds in sr_search_options.mutation_weights order (SR_MUT_*)
@@ -293,6 +295,16 @@ def _load():
             c_int,
             [c_int, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), c_int64,
              c_int64, P, P, POINTER(c_int), P, c_int64],
+        ),
+        "sr_compile_info_grad": (
+            c_int,
+            [c_int, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), c_int64,
+             c_int64, P, P, POINTER(c_int), P, c_int64],
+        ),
+        "sr_compile_info_grad_parametric": (
+            c_int,
+            [c_int, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), POINTER(SrParamBatch),
+             c_int64, c_int64, P, P, POINTER(c_int), P, c_int64],
         ),
         "sr_host_unary": (c_int, [c_int, c_char_p, c_int64, P, P]),
         "sr_last_kernel_ms": (c_int, [P, POINTER(c_double), POINTER(c_double)]),

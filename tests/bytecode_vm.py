@@ -18,8 +18,11 @@ B = dict(ADD=1, SUB=2, MUL=3, DIV=4)
 MAX_EXP = {np.float32: np.float32(88.72284), np.float64: 709.7827128933841}
 
 
-def compile_info(options, tb, n_rows, nfeatures, dtype):
-    un = (ctypes.c_char_p * max(1, len(options.operators.unaops)))(*[s.encode() for s in options.operators.unaops])
+def compile_info(options, tb, n_rows, nfeatures, dtype, grad=False):
+    """(code, offsets, static_bad, max_depth) of the LOSS programs, or with ``grad`` of the GRADIENT programs
+    the forward-mode kernels run (sr_compile_info_grad: constants live, no fusion, constant operands carry
+    their pre-order slot in the operand index).  A parametric batch goes through the parametric entry points."""
+    un =(ctypes.c_char_p * max(1, len(options.operators.unaops)))(*[s.encode() for s in options.operators.unaops])
     bi = (ctypes.c_char_p * max(1, len(options.operators.binops)))(*[s.encode() for s in options.operators.binops])
     nt = tb.n_trees
     lens = np.zeros(nt, dtype=np.int32)
@@ -31,10 +34,16 @@ def compile_info(options, tb, n_rows, nfeatures, dtype):
     rec = np.dtype([("op", "<u4"), ("meta", "<u4"), ("val", "<f4"), ("c1", "<u4")]) if dtype == np.float32 else \
         np.dtype([("op", "<u4"), ("meta", "<u4"), ("val", "<f8")], align=False)
     code = np.zeros(cap, dtype=rec)
-    _lib.check(_lib.lib.sr_compile_info(dt, len(options.operators.unaops), un, len(options.operators.binops), bi,
-                                        ctypes.byref(s), n_rows, nfeatures, lens.ctypes.data_as(ctypes.c_void_p),
-                                        bad.ctypes.data_as(ctypes.c_void_p), ctypes.byref(depth),
-                                        code.ctypes.data_as(ctypes.c_void_p), cap))
+    head = (dt, len(options.operators.unaops), un, len(options.operators.binops), bi, ctypes.byref(s))
+    tail = (n_rows, nfeatures, lens.ctypes.data_as(ctypes.c_void_p), bad.ctypes.data_as(ctypes.c_void_p),
+            ctypes.byref(depth), code.ctypes.data_as(ctypes.c_void_p), cap)
+    if tb.parametric:
+        ps = tb.to_param_struct()
+        fn = _lib.lib.sr_compile_info_grad_parametric if grad else _lib.lib.sr_compile_info_parametric
+        _lib.check(fn(*head, ctypes.byref(ps), *tail))
+    else:
+        fn = _lib.lib.sr_compile_info_grad if grad else _lib.lib.sr_compile_info
+        _lib.check(fn(*head, *tail))
     offs = np.concatenate([[0], np.cumsum(lens)])
     return code, offs, bad.astype(bool), int(depth.value)
 
