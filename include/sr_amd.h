@@ -591,8 +591,7 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * events behind sr_last_kernel_ms / sr_last_phase_ms), "rows_per_lane" (0: the default kernel per
  * call; Float32 16 / 32 force the register-stack kernel and 4 / 8 the LDS-stack one, Float64 8 / 4
  * likewise), "balance" (0 / 1: deal the cost-ordered trees round-robin over tree groups),
- * "fused_reduce" (the largest tree group, in trees x row blocks, whose partials the interpreter launch
- * reduces itself — its last workgroup per group; 0: always a separate reduce launch), "exact_w" (4 / 1:
+ * "exact_w" (4 / 1:
  * waves per workgroup of the exact-sum pass), "exact_g" (listed trees per exact-sum workgroup; 0: the
  * heuristic), "fold_seg" (rows per segment of the in-order loss fold: -1 automatic, 0 one workgroup
  * scan over every row per tree, as rounds 3-4), "ref_fold" (1, the default: every complete tree's loss
@@ -626,7 +625,8 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * C4's 2^26 rows — keeps the f64 sum, as "ref_fold" 0).  Results do not depend on any knob but these
  * three ("ref_fold", "fold_seg_max", "fold_rows_max": whether a call folds) and — without the fold only
  * — "max_row_blocks", which sets how many f64 partials a tree's sum adds (the last bit of a loss may
- * differ).  SR_ERR_INVALID_ARG for an unknown name.  sr_tuning_info (optional outputs)
+ * differ).  SR_ERR_INVALID_ARG for an unknown name.  Every knob's name, environment variable, default and
+ * range are stated once, in csrc/sr_knobs.h: that table is the authority.  sr_tuning_info (optional outputs)
  * reports how many derived columns the last sr_eval_loss_batch used and how many of its trees went
  * through the exact-sum pass (flagged BIG). */
 int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value);

@@ -23,8 +23,8 @@ __global__ void __launch_bounds__(256) sr_reduce_partials_kernel(const double* _
   const int lane = int(threadIdx.x) & 63;
   const int pos = int(int64_t(blockIdx.x) * (blockDim.x / 64) + threadIdx.x / 64);
   if (pos >= n_trees) return;  // wave-uniform
-  sr_reduce_positions<1, false>(part_sum, part_flag, n_trees, n_row_blocks, pos, 1, 1, perm, static_bad, out_sum,
-                                out_flag, lane);
+  sr_reduce_positions<1>(part_sum, part_flag, n_trees, n_row_blocks, pos, 1, 1, perm, static_bad, out_sum, out_flag,
+                         lane);
 }
 
 // Julia's pairwise `sum` of one view, from its leaf folds: every thread combines one array's
@@ -908,8 +908,8 @@ __global__ void __launch_bounds__(256) sr_reduce_partials_excl_kernel(const doub
     }
     return;
   }
-  sr_reduce_positions<1, false>(part_sum, part_flag, n_trees, n_row_blocks, pos, 1, 1, perm, static_bad, out_sum,
-                                out_flag, lane);
+  sr_reduce_positions<1>(part_sum, part_flag, n_trees, n_row_blocks, pos, 1, 1, perm, static_bad, out_sum, out_flag,
+                         lane);
 }
 hipError_t sr_launch_reduce_excl(const double* part_sum, const uint32_t* part_flag, int n_trees, int n_row_blocks,
                                  const uint32_t* perm, const uint8_t* static_bad, const uint8_t* excl, double* out_sum,
@@ -1057,7 +1057,7 @@ __global__ void __launch_bounds__(64) sr_fold_stab_kernel(const double* __restri
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) pre += __shfl_xor(pre, off, 64);
   const double sb = (who.est ? who.est[t] : 0.0) + pre;  // (an estimate: it only chooses binades)
-  const double sa = sb + (part ? part[o] : who.sums[t]);  // (one row block: the view's total; no fused reduce)
+  const double sa = sb + (part ? part[o] : who.sums[t]);  // (one row block: the view's total)
   const int q = sr_fold_q<T>(sb * (1.0 - delta));
   const bool slow = q != sr_fold_q<T>(sa * (1.0 + delta));
   const int64_t lo = int64_t(rb) * rb_rows, hi = lo + rb_rows < n ? lo + rb_rows : n;

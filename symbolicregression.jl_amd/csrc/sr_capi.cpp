@@ -30,6 +30,7 @@
 #include "sr_eval.h"
 #include "sr_fold.h"
 #include "sr_fold_dev.h"
+#include "sr_knobs.h"
 #include "sr_param_pack.h"
 
 namespace {
@@ -49,9 +50,14 @@ int set_error(int code, const std::string& msg) {
       return set_error(SR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));              \
   } while (0)
 
+// A device allocation that grows on demand and belongs to whatever holds it (the context: freed with it).
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) {
@@ -82,6 +88,10 @@ struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
   unsigned flags = hipHostMallocDefault;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() { release(); }
   hipError_t ensure(size_t bytes, hipStream_t s, hipStream_t s2) {
     if (bytes <= cap) return hipSuccess;
     if (p) {
@@ -132,7 +142,8 @@ inline bool loss_direct_ok(int kind) {
 // the thread-local error message, for the other translation units of the library (sr_search.cpp)
 int sr_set_error(int code, const std::string& msg) { return set_error(code, msg); }
 
-struct sr_ctx {
+// The context: its tuning knobs (SrKnobs, sr_knobs.h) and its streams, events, buffers and last-call records.
+struct sr_ctx : SrKnobs {
   int device = 0;
   hipStream_t stream = nullptr;
   // second stream of the chunked pipeline (odd chunks), created on the first chunked call: a HIP
@@ -142,17 +153,7 @@ struct sr_ctx {
   hipError_t need_stream2() {
     return stream2 ? hipSuccess : hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking);
   }
-  // SR_AMD_TAIL_CHUNK / "tail_chunk": a plain path-2 call whose loss launch composes candidates (C2's) runs
-  // three chunks {1 / first_chunk, the rest, tail_chunk / 12} of the trees (sr_chunk_plan): the last two loss
-  // launches end close together and their fold chains — latency-bound, each on its chunk's stream — run
-  // side by side instead of one chain of 5/6 of the trees alone; 0: the two-chunk schedule
-  int tail_chunk = 4;
-  // SR_AMD_EXACT_EARLY / "exact_early": a multi-chunk loss call under the in-order fold copies its flags to
-  // pinned memory behind the last chunk's reduce (every chunk's flags are final there) and records ev_flags;
-  // eval_loss_finish waits for that event alone, lists the BIG trees and enqueues the exact-sum pass on a
-  // third stream, which no chain occupies, so the pass runs beside the last chains; the call's one full
-  // synchronisation follows.  0: the pass after that synchronisation, as before
-  int exact_early = 1;
+  // (the exact_early knob's state, sr_knobs.h)
   bool want_early = false;  // set by eval_loss_submit around its run_batch
   bool early_last = false;  // the last run_batch copied the flags early (and left the results' copy to the caller)
   hipEvent_t ev_flags = nullptr;
@@ -184,21 +185,12 @@ struct sr_ctx {
   int64_t n_fold_last = 0;   // trees of the last eval_loss call whose loss fold was computed in order (sr_fold.h)
   int64_t fold_slow_last = 0;  // ... their segments folded row by row (the rest: composed steps)
   int64_t fold_seg_last = 0;   // ... and the segment length used
-  int64_t fold_seg = -1;       // SR_AMD_FOLD_SEG / sr_set_tuning "fold_seg": -1 automatic, 0 one scan per tree
   double exact_kernel_ms = 0.0;  // device time of that pass (its interpreter + combine launches)
   // programs + per-tree metadata of the last run_batch: ONE device allocation and ONE pinned staging
   // buffer with the same layout (code | offsets | static_bad | launch order), so a single-chunk call
   // uploads with one DMA; per-tree {Σ loss, flags} likewise share one allocation (one DMA back)
   HostBuf h_prog, h_outs, h_grad;  // (h_grad: the gradient call's staging image, then its results)
-  // Small calls with several row blocks (round 5, SR_AMD_HOST_REDUCE / "host_reduce"): the
-  // interpreter writes its per-(row block, tree) partials straight into pinned host memory (h_part)
-  // and the host reduces them after the one stream synchronisation, in the reduce kernel's own order
-  // (sr_reduce_positions: lane l folds row blocks l, l + 64, ...; a shfl_xor butterfly over the 64
-  // lanes), so the bits are the reduce launch's; a C3 scoring call loses that launch and its gap.
-  // The bound is on the call's partials (trees x row blocks): a C3 / C5 scoring call has ~1,600; a
-  // 1,250-tree x 256-row-block call (320k partials) wrote 3.8 MB over PCIe and spent ~1 ms reducing on
-  // the host (tools/share_probe.py: 2.47 ms per call against 1.1 with the reduce launch).
-  int64_t host_reduce = 8192;
+  // the host_reduce knob's (sr_knobs.h) pinned partials and the launches that wrote them
   HostBuf h_part;
   struct HostReduction {
     int64_t p0, np;
@@ -218,22 +210,10 @@ struct sr_ctx {
   double* d_out_sum = nullptr;
   uint32_t* d_out_flag = nullptr;
   size_t outs_flag_off = 0;
-  // Small single-chunk LOSS calls (the search's regime: tens of trees, ~100 rows) are latency-bound:
-  // SR_AMD_HOST_IO = 1 (default) lets the kernel write the per-tree results straight into pinned
-  // host memory (no copy back); 0 copies them.  (Round 5's 2 — programs read from the pinned staging
-  // buffer — was measured without payoff and removed in round 6.)
-  int host_io = 1;
-  bool want_host_out = false;  // set by eval_loss_impl around its run_batch
+  bool want_host_out = false;  // (host_io) set by eval_loss_impl around its run_batch
   bool outs_on_host = false;   // the last run_batch wrote {Σ, flags} to h_outs
   uint32_t hint_epoch = 0;  // dead-tree hint epoch of the current call
-  int debug_hint_regrow = 0;       // tests (sr_set_tuning "debug_hint_regrow"): grow the hint array in place
-  void* hint_reserve = nullptr;    // its fixed-address reservation
-  int exact_g = 0;          // SR_AMD_EXACT_G (tuning): listed trees per workgroup of the EXACT pass
-  int exact_w = 4;          // SR_AMD_EXACT_W / sr_set_tuning "exact_w": waves per EXACT workgroup (4, or 1)
-  int par_stage = 1;        // SR_AMD_PAR_STAGE: large chunks' programs copied to the staging buffer in parallel
-  // SR_AMD_DERIVED (default 1): nodes unary(feature) shared by several trees of a large LOSS call
-  // are evaluated once per call into derived columns (LOAD_DERIVED); 0 disables
-  int derived = 1;
+  void* hint_reserve = nullptr;    // debug_hint_regrow's fixed-address reservation
   std::mutex mu;
   std::vector<SrOpset> opsets;
   std::vector<int> tiers;
@@ -259,38 +239,20 @@ struct sr_ctx {
     }
   };
   std::deque<LossExpr> loss_exprs;  // (a deque: a call keeps a pointer to its entry while others register)
-  DevBuf prog, outs, part_sum, part_flag, pred, row_idx, tree_list,
+  DevBuf prog, outs, part_sum, part_flag, pred, row_idx,
       range_lo, range_hi, range_sums, packed, hint, jsum_prog, jsum_scratch, probe_sum, probe_flag, g_code, g_offsets, g_consts, g_const_off, g_items, g_part, g_out,
       derived_cols, probe_derived, fold_io;
   // The exact-sum pass's small transfers (round 5): the leaf ranges and the Julia-sum level program
   // depend only on the view's row count, so they stay on the device between calls (host mirrors below;
-  // a buffer that grows loses them); the tree list goes up and the verdicts come back through pinned
-  // memory.  Pageable copies cost ~15 us each, and a one-tree pass made five of them.
+  // a buffer that grows loses them); the pass reads its tree list from pinned memory and the verdicts come
+  // back through it.  Pageable copies cost ~15 us each, and a one-tree pass made five of them.
   HostBuf h_exact;
   std::vector<int64_t> exact_lo_dev, exact_hi_dev;  // what range_lo / range_hi hold
   int64_t jsum_n_dev = -1;                          // the row count jsum_prog was built for
-  // SR_AMD_EXACT_LIST_HOST (default 1): the pass reads its tree list from the pinned staging buffer
-  // (no upload ahead of the kernel); 0 copies it to the device first
-  int exact_list_host = 1;
 #ifdef SR_STAMPS
   DevBuf stamps;  // latency-analysis builds: the last main launch's per-wave stamps (sr_debug_stamps)
   int64_t n_stamps = 0;
 #endif
-  int stress_probe = 1;  // SR_AMD_STRESS_PROBE: the probe runs the dataset's stress rows (below)
-  int code_cache = 1;    // SR_AMD_CODE_CACHE: LDS program cache of the register-stack launches (0: off)
-  // SR_AMD_FUSED_REDUCE: multi-row-block LOSS launches reduce their partials in the launch (the last
-  // workgroup of a tree group) when the group holds at most this many partials; 0 (default): a reduce
-  // launch — measured faster: every workgroup's drained stores + barrier + counter add cost more than
-  // the launch they save (C3 search 14.4 vs 13.3 iterations/s, C2's dead trees 0.52 vs 0.71 ms;
-  // profiles/r04_ab_fused_reduce.txt)
-  int64_t fused_reduce = 0;
-  int vstk_rows = 0;        // SR_AMD_VSTK_ROWS / "vstk_rows": rows per lane of the register-stack kernel (0: default)
-  int grad_rows_force = 0;  // SR_AMD_GRAD_ROWS / "grad_rows": the gradient kernel's rows per lane (0: chosen per call)
-  int grad_sort = 1;        // SR_AMD_GRAD_SORT / "grad_sort": gradient work items ordered by program cost
-  int grad_lane_bins = 1;   // "grad_lane_bins": parametric gradients bin small slots x classes per lane (sr_eval.h)
-  DevBuf group_cnt;      // its per-group counters (zeroed at allocation; each launch leaves them zero)
-  int first_chunk = 6;   // SR_AMD_FIRST_CHUNK: the two-chunk pipeline's first chunk is 1/first_chunk
-  int64_t chunk_min = 1024;  // SR_AMD_CHUNK_MIN: the two-chunk pipeline runs when its first chunk holds this many trees
   // data-path transport of the sharded calls: the library's own RCCL over xGMI on its own HIP runtime
   // (sr_comm_init; torch's bundled runtime cannot share the GPU with this one in a process), or the
   // caller's host collectives (sr_comm_init_host)
@@ -302,16 +264,11 @@ struct sr_ctx {
   // shard layout / exact-pass folds / loss-fold chain / tree results, the packed partials, the agree word
   DevBuf coll_buf, coll_packed, ctl;
   HostBuf h_coll;        // pinned staging of the tree-sharded results
-  int inject_fail = 0;   // tests (sr_set_tuning "inject_failure"): the next k collective-buffer growths fail
-  int inject_post = 0;         // tests ("inject_failure_post"): a HIP failure right after the sharded all-reduce
-  int inject_post_exact = 0;   // tests ("inject_failure_post_exact"): ... after the exact-sum all-gather
-  int inject_post_gather = 0;  // tests ("inject_failure_post_gather" k): this rank's copy of the k-th fold gather fails
   double last_eval_ms = 0.0, last_total_ms = 0.0;
   double last_busy_ms = 0.0;  // union of the last call's interpreter launch intervals (sr_last_phase_ms out[8])
   // the two above are read from the last call's events lazily, when asked for (sr_last_kernel_ms /
   // sr_last_phase_ms): a small call (the search's) does not pay the event queries it never reads
   bool timing_pending = false;
-  int timing = 1;           // 0: no timing events at all (sr_set_tuning "timing"; the search engine's calls)
   bool timed_last = false;  // the last run_batch recorded its events
   // host-side phases of the last eval_loss call (ms): compile, upload+launch, wait, exact pass,
   // finalize (sr_last_phase_ms)
@@ -329,103 +286,33 @@ struct sr_ctx {
     phase_t = now;
   }
   int cu_count = 256;
-  int rows_override = 0;    // SR_AMD_ROWS_PER_LANE (tuning): 4 selects the f32 BASIC 4-rows/lane kernel
-  int tree_group = 0;       // SR_AMD_TREES_PER_BLOCK override (0 = heuristic)
   int rows_last = 0;        // rows per lane of the last interpreter call (sr_last_phase_ms out[7])
-  int waves_override = 0;   // SR_AMD_WAVES (tuning): 8 selects the 8-wave f32 BASIC L2 loss kernel
-  bool cost_order = true;   // launch trees in decreasing estimated cost (SR_AMD_NO_SORT=1 disables)
-  bool balance_groups = true;  // deal the cost order round-robin over tree groups (SR_AMD_BALANCE=0: contiguous)
-  bool dead_hints = true;   // share dead-tree hints across row blocks (SR_AMD_NO_HINT=1 disables)
-  // SR_AMD_MAX_ROW_BLOCKS (tuning): upper bound on row blocks per tree.  512 since round 5 (A/B, three
-  // alternating passes on one box, profiles/r05_ab_row_blocks.txt): C2 4.47 vs 4.51 ms per step, C4
-  // 1,520 vs 1,533 ms, the tree-sharding share (1,250 trees) 1.03 vs 1.09 ms: a small population keeps
-  // 128 trees per workgroup instead of halving it to fill the GPU.  Results do not depend on it only
-  // up to the f64 summation order of the partials (row blocks are a function of the rows alone).
-  int max_row_blocks = 512;
-  int chunks = 2;           // SR_AMD_CHUNKS: pipeline compile/launch over this many tree chunks (1 = off)
-  int probe = 2;            // dead-tree probe launch (SR_AMD_PROBE): 0 off, 1 before every chunk,
-                            // 2 (default) only before the chunks after the first, whose probe
-                            // overlaps the first chunk's kernel (profiles/r01_ab_probe_modes.txt)
   std::vector<uint32_t> perm_host;
-  // The reference's in-order loss fold for EVERY complete tree (round 6; sr_fold_dev.h, sr_aux.hip): a
-  // complete tree's loss is LossFunctions' left-to-right fold in T of its elementwise losses
-  // (src/LossFunctions.jl:38-58), divided in T, not the device's f64 sum.  SR_AMD_REF_FOLD / "ref_fold":
-  // 1 (default) single-GPU loss calls with weights >= 0; 0 the f64 sums (rounds 1-5).  Small calls
-  // (every tree's losses fit fold_store_mb) keep the loss launch's losses; larger Float32 calls run the
-  // complete trees again in FOLD mode (slow segments' losses in up to fold_slot_mb of slots); larger
-  // Float64 calls, and calls whose row blocks pass fold_seg_max rows (C4: 2^26 rows per GPU), keep the f64
-  // sum (Float64: within ~1e-13 of the fold, north_star's f64 bar is 1e-10).
-  int ref_fold = 1;
-  int64_t fold_store_mb = 512;
-  int64_t fold_slot_mb = 24576;  // (allocated as needed: ~24 slots per tree; C4's 2^26 rows take ~21 GB)
-  // the plan's window: the fold within 2^-8 of the f64 prefix, else the tree fails (C2's trees: the fold is
-  // within 2.1e-3 of the f64 sum at 2^20 rows; 2^-6 kept twice the slow segments)
-  int fold_delta_log2 = 8;
-  int64_t fold_seg_max = 16384;  // SR_AMD_FOLD_SEG_MAX: calls whose row blocks are longer keep the f64 sum
-  int64_t fold_rows_max = int64_t(1) << 24;  // SR_AMD_FOLD_ROWS_MAX: longer folds keep the f64 sum
-  int fold_debug_fail = 0;   // (tests: "fold_debug_fail")
-  int fold_reduce = 1;       // SR_AMD_FOLD_REDUCE: stored-loss folds reduce in the pair kernel (0: a reduce launch)
-  int fold_pre_start = 1;    // SR_AMD_FOLD_PRE_START: stored-loss folds start in the pair kernel (0: in the walk)
-  // SR_AMD_FOLD_SINGLE_PASS / "fold_single_pass": the loss launch of a FOLD-mode call (path 2) composes each
-  // row block's steps under candidate binades, and the plan takes the blocks whose binade is among
-  // them, so the FOLD pass runs only what is left (0: every block of every complete tree again).  Plain
-  // single-GPU Float32 BASIC calls over the full view, register-stack launch; every other call keeps the
-  // two passes.
-  int fold_single_pass = 1;
-  DevBuf fold_cand;          // the candidates, [row block][position] int4 (sr_fold_dev.h)
-  // SR_AMD_FOLD_COMPACT / "fold_compact": the FOLD pass of a plain path-2 call runs over per-row-block lists
-  // of the positions the plan left it (sr_fold_compact_kernel), G per workgroup, instead of the loss
-  // launch's (row block, tree group) grid (0).  Gathered, parametric and row-sharded calls keep the grid.
-  int fold_compact = 1;
-  DevBuf fold_list;          // [row block][position] int32, laid out as the partials
+  // The in-order loss fold's buffers and last-call records (the ref_fold and fold_* knobs: sr_knobs.h)
+  DevBuf fold_cand;          // (fold_single_pass) the candidates, [row block][position] int4 (sr_fold_dev.h)
+  DevBuf fold_list;          // (fold_compact) [row block][position] int32, laid out as the partials
   DevBuf fold_wg;            // per region (2 per chunk): {cnt [n_rb], wg0 [n_rb + 1], g}
-  // SR_AMD_FOLD_LIST_WGS / "fold_list_wgs": the live workgroups a compacted FOLD launch aims for.  Its list's
-  // entries per workgroup g is chosen on the device from the row blocks' counts (sr_fold_compact_scan_kernel,
-  // sr_plan.h's sr_fold_list_g): the smallest multiple of the 4 waves that keeps the launch within this many
-  // workgroups and within its grid.  0: g = G, the launch's trees per workgroup — C2's row blocks list ~100
-  // positions each, so one workgroup per row block, ~27 trees a wave in turn on half the GPU's wave slots.
-  // Smaller g: more workgroups stage a row block's tiles for fewer trees each.
-  int64_t fold_list_wgs = 2048;
   // the last call's compacted FOLD launches: per region its row blocks (0: none) and the call's row blocks per
   // position, for sr_last_phase_ms out[19..] (read back once on request)
   int fold_wg_nrb[2 * kMaxChunks] = {};
   int64_t fold_wg_stride_rb = 0;
   bool fold_wg_read = true;
   double fold_wg_info[2 * kMaxChunks][4] = {};  // {live workgroups, listed entries, g, the longest list}
-  // SR_AMD_LOSS_COMPACT / "loss_compact": the candidate-composing loss launch of such a call runs over the
-  // launch positions its chunk's dead-tree probe left alive, less the statically incomplete trees
-  // (sr_loss_compact_kernel: one list per launch, dealt over the launch's tree groups, the live workgroups
-  // first), and the reduce gives the excluded positions their result without reading a partial (0: every
-  // position, the launch sequence before the list).
-  int loss_compact = 1;
-  // SR_AMD_LOSS_LIST_GROUPS / "loss_list_groups": the most tree groups a listed launch deals its list over (0,
-  // the default: all of its grid's; sr_loss_compact_kernel: fewer groups = fewer workgroups to stage tiles,
-  // but the candidates' guess from the running prefix lags by resident workgroups / groups row blocks, and
-  // which of a call's overlapping launches ends last moves with it: DESIGN.md §12)
-  int loss_list_groups = 0;
-  DevBuf loss_list;          // {list int32 [nt] | cnt int32 [kMaxChunks][4] | excl uint8 [nt]} (sr_plan.h)
+  DevBuf loss_list;          // (loss_compact) {list int32 [nt] | cnt int32 [kMaxChunks][4] | excl uint8 [nt]} (sr_plan.h)
   // the last call's listed launches: per chunk the launch's positions (0: not listed), and the counters read
   // back once on request (sr_last_phase_ms out[16..18])
   int64_t loss_listed_np[kMaxChunks] = {0, 0, 0, 0};
   int64_t loss_list_nt_last = 0;
   bool loss_list_read = true;
   int64_t n_loss_listed_launches_last = 0, n_loss_live_last = 0, n_loss_excl_last = 0;
-  // SR_AMD_FOLD_CAND_EST / "fold_cand_est": the candidates' guess from the tree's running prefix (the row
-  // blocks other workgroups have finished; 0: the block's first tile only); usable from fold_cand_est_min
-  // finished blocks on (SR_AMD_FOLD_CAND_EST_MIN; tools/fold_cand_sim.py)
-  int fold_cand_est = 1;
-  int fold_cand_est_min = 4;
-  DevBuf fold_est;           // per launch position: {f64 sum [nt] | u32 count [nt]}, zeroed by every call
+  DevBuf fold_est;           // (fold_cand_est) per launch position: {f64 sum [nt] | u32 count [nt]}, zeroed by every call
   bool fold_cand_read = true;  // fold_ctl's counters of the last call are in n_cand_* below
   int64_t n_cand_taken_last = 0, n_cand_rerun_last = 0;
-  int fold_walk_dbg = 0;     // SR_AMD_FOLD_WALK_DBG (analysis): 2 no O(1) slow blocks, 4 no serial start
-  int fold_stats = 0;        // SR_AMD_FOLD_STATS=1: per-tree walk statistics to stderr after each call (analysis)
-  DevBuf fold_dbg;
+  DevBuf fold_dbg;           // (fold_stats)
   bool want_fold = false;    // set by eval_loss_submit around its run_batch
   int fold_path_last = 0;    // 0 none, 1 stored losses, 2 FOLD mode
   DevBuf fold_code, fold_tab, fold_store, fold_ctl, fold_io2, fold_sq, fold_tab2;
   std::shared_ptr<void> fold_job;  // a row-sharded call's FoldJob<T>, until its ranks agree on the verdicts
-  int inject_post_wsum = 0;        // tests ("inject_failure_post_wsum"): this rank's copy of the weights' sum gather fails
   size_t outs_fval_off = 0, outs_fst_off = 0, outs_bytes_all = 0;
   hipEvent_t ev_fc0[kMaxChunks] = {}, ev_fc1[kMaxChunks] = {};  // each chunk's fold launches
   bool fold_timed_last = false;
@@ -664,7 +551,6 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
   fa.hint = nullptr;
   fa.out_sum = nullptr;
   fa.out_flag = nullptr;
-  fa.group_cnt = nullptr;
   fa.stamps = nullptr;
   fa.fold_code = ft.code;
   fa.fold_tab = ft.tab;
@@ -712,7 +598,7 @@ int fold_walk(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFol
   const int nrb = fr.g.n_row_blocks;
   const int tiny = carry == nullptr && fold_tiny(job, fr, who) ? 16 : 0;
   // (stored losses, the pair kernel launched, the fold starting here: it did the serial start)
-  const int pre = job.path == 1 && !tiny && carry == nullptr && who.first && ctx->fold_pre_start ? 32 : 0;
+  const int pre = job.path == 1 && !tiny && carry == nullptr && who.first ? 32 : 0;
   who = fold_who_at(who, fr.t0);
   const int64_t rb_rows = fr.rb_rows();
   const SrFoldTabs ft = fr.tabs(ctx, job.n_rb);
@@ -723,7 +609,7 @@ int fold_walk(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFol
   for (int pass = 0; pass < (ctx->fold_stats == 2 ? 2 : 1); ++pass)
     SR_HIP_CHECK(sr_launch_fold_walk<T>(ft, who, int(fr.np), nrb, rb_rows, job.n_eval, losses, slot_rows, fr.a.perm,
                                         carry ? carry + fr.t0 : nullptr, out_val + fr.t0, out_st + fr.t0, dbg,
-                                        int(job.path == 1) | tiny | pre | ctx->fold_walk_dbg, cs));
+                                        int(job.path == 1) | tiny | pre, cs));
   return SR_OK;
 }
 
@@ -970,11 +856,6 @@ struct BatchCall {
     n_part = size_t(nt) * size_t(n_rb);
     SR_HIP_CHECK(ctx->part_sum.ensure(n_part * sizeof(double) + 8));
     SR_HIP_CHECK(ctx->part_flag.ensure(n_part * sizeof(uint32_t) + 4));
-    if (mode == SR_MODE_LOSS && ctx->fused_reduce > 0 && size_t(nt) * sizeof(uint32_t) + 4 > ctx->group_cnt.cap) {
-      SR_HIP_CHECK(hipStreamSynchronize(s));  // (the second stream runs only inside a call)
-      SR_HIP_CHECK(ctx->group_cnt.ensure(size_t(nt) * sizeof(uint32_t) + 4));
-      SR_HIP_CHECK(hipMemset(ctx->group_cnt.p, 0, ctx->group_cnt.cap));
-    }
     return SR_OK;
   }
 
@@ -1254,9 +1135,8 @@ struct BatchCall {
     fjob.slot_rows = fold.slot_rows;
     fjob.n_terms = fold_n_terms;
     fjob.delta = std::ldexp(1.0, -ctx->fold_delta_log2);
-    // stored losses on one GPU: the pair kernel reduces the partials itself (one launch fewer a call;
-    // SR_AMD_FOLD_REDUCE=0: the reduce launch)
-    fjob.fuse_reduce = fold.path == 1 && !shard && mode == SR_MODE_LOSS && ctx->fold_reduce;
+    // stored losses on one GPU: the pair kernel reduces the partials itself (one launch fewer a call)
+    fjob.fuse_reduce = fold.path == 1 && !shard && mode == SR_MODE_LOSS;
     fjob.slot_cap = fold.path == 2
                         ? int(std::min<int64_t>({int64_t(INT_MAX / 2), fold.slot_budget,
                                                  int64_t(ctx->fold_store.cap / (size_t(fold.slot_rows) * sizeof(T)))}))
@@ -1339,7 +1219,7 @@ struct BatchCall {
       }
     };
     constexpr int64_t kCopyPiece = 512;
-    if (ctx->par_stage && nc >= 4 * kCopyPiece) {
+    if (nc >= 4 * kCopyPiece) {
       sr_parallel_for(int((nc + kCopyPiece - 1) / kCopyPiece), [&](int w) {
         const int64_t p0 = int64_t(w) * kCopyPiece;
         copy(p0, std::min<int64_t>(nc, p0 + kCopyPiece));
@@ -1384,7 +1264,7 @@ struct BatchCall {
 
   // The argument blocks of one launch over launch positions [p0, p0 + np) of the chunk; its partials
   // occupy [n_rb][np] words from p0 * n_rb (the chunk's region holds n_rb rows for every position).
-  // out_sum / group_cnt (the reduce's routing), segs and fold_cand are the launch's own (launch_region).
+  // out_sum (the reduce's routing), segs and fold_cand are the launch's own (launch_region).
   void fill_region_args(const BatchChunk<T>& ch, int64_t p0, int64_t np, bool vstk, const Grid& g,
                         SrEvalArgs<T>* out, SrParamArgs<T>* pout) {
     const int64_t t0 = ch.t0;
@@ -1484,7 +1364,6 @@ struct BatchCall {
     pa.out_sum = nullptr;
     pa.out_flag = nullptr;
     pa.code_lds = 0;  // (its groups differ from the main launch's)
-    pa.group_cnt = nullptr;
     pa.stamps = nullptr;
     pa.trees_per_block = std::max(16, g.W);
     pa.n_groups = int((np + pa.trees_per_block - 1) / pa.trees_per_block);
@@ -1538,15 +1417,6 @@ struct BatchCall {
       a.out_flag = ctx->d_out_flag + t0;
       a.static_bad = ctx->d_bad + t0;
     }
-    // several row blocks: the last workgroup of each tree group reduces it (no reduce launch)
-    const bool fused = !direct && !host_red && mode == SR_MODE_LOSS && ctx->fused_reduce > 0 &&
-                       int64_t(g.G) * int64_t(g.n_row_blocks) <= ctx->fused_reduce;
-    if (fused) {
-      a.group_cnt = ctx->group_cnt.as<uint32_t>() + t0 + p0;
-      a.fused_sum = ctx->d_out_sum + t0;
-      a.fused_flag = ctx->d_out_flag + t0;
-      a.static_bad = ctx->d_bad + t0;
-    }
     // mode 2 (default): every chunk after the first (its probe overlaps the first chunk's kernel),
     // and a single-chunk call when it is large (>= 512 trees x 2^18 rows: the tree-sharding share,
     // 1,250 trees x 1M rows, 1.09 -> 1.01 ms; the search's small calls pay the probe's launch and
@@ -1573,7 +1443,7 @@ struct BatchCall {
     }
     // the listed launch (sr_ctx::loss_compact): the candidate launch of a region whose probe has just run on
     // this stream, reduced by a reduce launch; the list from the hints as the probe left them
-    const bool listed = loss_compact && cand_launch && probed && !direct && !fused && !host_red && !fjob.fuse_reduce &&
+    const bool listed = loss_compact && cand_launch && probed && !direct && !host_red && !fjob.fuse_reduce &&
                         !parametric && !multi;
     uint8_t* excl = nullptr;
     if (listed) {
@@ -1600,19 +1470,19 @@ struct BatchCall {
     else
       SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
     if (fold.path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g, fold_compact ? sr_fold_region(ch.c, vstk) : -1});
-    if (!direct && !fused && host_red)
+    if (!direct && host_red)
       ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
     else if (listed)
       SR_HIP_CHECK(sr_launch_reduce_excl(a.part_sum, a.part_flag, int(np), g.n_row_blocks, a.perm, ctx->d_bad + t0, excl,
                                          ctx->d_out_sum + t0, ctx->d_out_flag + t0, cs));
-    else if (!direct && !fused && !fjob.fuse_reduce)
+    else if (!direct && !fjob.fuse_reduce)
       SR_HIP_CHECK(sr_launch_reduce(a.part_sum, a.part_flag, int(np), g.n_row_blocks, a.perm, ctx->d_bad + t0,
                                     ctx->d_out_sum + t0, ctx->d_out_flag + t0, cs));
     return SR_OK;
   }
 
   // the in-order fold of this chunk's complete trees (sr_aux.hip): the launches' partials and flags
-  // are final here (reduce / direct write / in-launch reduction ran on this stream)
+  // are final here (reduce / direct write ran on this stream)
   int fold_chunk(const BatchChunk<T>& ch) {
     hipStream_t cs = ch.cs;
     if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_fc0[ch.c], cs));
@@ -2009,16 +1879,12 @@ int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, 
     if (lds > kLdsMax) return set_error(SR_ERR_TOO_DEEP, "exact-sum pass needs more LDS than 160 KiB");
     uint32_t* list32 = reinterpret_cast<uint32_t*>(hx + o_list);  // (the previous batch's pass has completed)
     for (int64_t i = 0; i < nb; ++i) list32[i] = uint32_t(list[b0 + i]);
-    if (!ctx->exact_list_host) {
-      SR_HIP_CHECK(ctx->tree_list.ensure(size_t(nb) * sizeof(uint32_t)));
-      SR_HIP_CHECK(hipMemcpyAsync(ctx->tree_list.p, list32, size_t(nb) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    }
     SR_HIP_CHECK(ctx->range_sums.ensure(size_t(nb) * per_tree));
     SrEvalArgs<T> a{};
     a.code = static_cast<const SrIns<T>*>(ctx->d_code);
     a.offsets = ctx->d_off;
     a.ends = ctx->d_end;
-    a.perm = ctx->exact_list_host ? list32 : ctx->tree_list.as<uint32_t>();
+    a.perm = list32;  // (read from the pinned staging buffer: no upload ahead of the kernel)
     a.n_trees = int(nb);
     a.trees_per_block = G;
     a.X = static_cast<const T*>(ds->X);
@@ -4066,6 +3932,54 @@ int eval_tree_sharded_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, cons
   return SR_OK;
 }
 
+// Every event of the context, stated once: f(event, timed) — sr_init creates them (timed: the event records
+// times; the others only order streams), destroy_ctx destroys them.
+template <typename F>
+void for_each_event(sr_ctx* ctx, F f) {
+  f(ctx->ev_join, false);
+  f(ctx->ev_flags, false);
+  for (hipEvent_t& ev : ctx->ev_red) f(ev, false);
+  for (hipEvent_t* ev : {&ctx->ev_start, &ctx->ev_k0, &ctx->ev_k1, &ctx->ev_end, &ctx->ev_d0, &ctx->ev_d1}) f(*ev, true);
+  for (int c = 0; c < kMaxChunks; ++c)
+    for (hipEvent_t* ev : {&ctx->ev_c0[c], &ctx->ev_c1[c], &ctx->ev_fc0[c], &ctx->ev_fc1[c]}) f(*ev, true);
+  for (int b = 0; b < sr_ctx::kGradBuckets; ++b)
+    for (hipEvent_t* ev : {&ctx->ev_g0[b], &ctx->ev_g1[b]}) f(*ev, true);
+  for (hipEvent_t& ev : ctx->ev_f) f(ev, true);
+}
+
+// The context's end (sr_shutdown, and sr_init when it fails part-way: what was never created is null and
+// skipped).  In the order the device sees: synchronise the streams, drop the transport, destroy the events
+// and streams, free the buffers — the DevBuf / HostBuf members free themselves in `delete`.
+void destroy_ctx(sr_ctx* ctx) {
+  {
+    Lock l(ctx);
+    (void)hipSetDevice(ctx->device);
+    for (hipStream_t s : {ctx->stream, ctx->stream2, ctx->stream3})
+      if (s) (void)hipStreamSynchronize(s);
+    ctx->xport.reset();
+    for_each_event(ctx, [](hipEvent_t& ev, bool) {
+      if (ev) (void)hipEventDestroy(ev);
+      ev = nullptr;
+    });
+    for (hipStream_t* s : {&ctx->stream3, &ctx->stream2, &ctx->stream}) {
+      if (*s) (void)hipStreamDestroy(*s);
+      *s = nullptr;
+    }
+    // (debug_hint_regrow: the hint array may live inside its reservation, which is freed once)
+    if (ctx->hint.p == ctx->hint_reserve) {
+      ctx->hint.p = nullptr;
+      ctx->hint.cap = 0;
+    }
+    if (ctx->hint_reserve) (void)hipFree(ctx->hint_reserve);
+    ctx->hint_reserve = nullptr;
+    for (sr_ctx::LossExpr& e : ctx->loss_exprs) {
+      if (e.dev) (void)hipFree(e.dev);
+      e.dev = nullptr;
+    }
+  }
+  delete ctx;
+}
+
 }  // namespace
 
 // ====================================================================== C ABI
@@ -4093,92 +4007,17 @@ int sr_init(int device, sr_ctx** out) {
   if (hipGetDeviceCount(&c) != hipSuccess || c <= 0) return set_error(SR_ERR_NO_DEVICE, "no HIP device visible");
   if (device < 0 || device >= c) return set_error(SR_ERR_INVALID_ARG, "device index out of range");
   SR_HIP_CHECK(hipSetDevice(device));
-  // SR_AMD_SCHED (A/B only): how the host waits for the device — spin / yield / block
-  if (const char* v = std::getenv("SR_AMD_SCHED")) {
-    const unsigned f = std::strcmp(v, "spin") == 0    ? hipDeviceScheduleSpin
-                       : std::strcmp(v, "yield") == 0 ? hipDeviceScheduleYield
-                       : std::strcmp(v, "block") == 0 ? hipDeviceScheduleBlockingSync
-                                                      : hipDeviceScheduleAuto;
-    const hipError_t e = hipSetDeviceFlags(f);
-    if (e != hipSuccess) std::fprintf(stderr, "[sr] hipSetDeviceFlags(%s): %s\n", v, hipGetErrorString(e));
-  }
   auto* ctx = new sr_ctx();
   ctx->device = device;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cu_count = prop.multiProcessorCount;
-  if (const char* v = std::getenv("SR_AMD_ROWS_PER_LANE")) ctx->rows_override = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_TREES_PER_BLOCK")) ctx->tree_group = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_WAVES")) ctx->waves_override = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_NO_SORT")) ctx->cost_order = std::atoi(v) == 0;
-  if (const char* v = std::getenv("SR_AMD_BALANCE")) ctx->balance_groups = std::atoi(v) != 0;
-  if (const char* v = std::getenv("SR_AMD_NO_HINT")) ctx->dead_hints = std::atoi(v) == 0;
-  // (A/B: the program staging buffer allocated non-coherent, so that kernels reading programs from it
-  //  — SR_AMD_HOST_IO=2 — may cache them in L2; the dispatch's acquire makes each call's writes visible)
-  if (const char* v = std::getenv("SR_AMD_CHUNKS")) ctx->chunks = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_PROBE")) ctx->probe = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_FOLD_SEG")) ctx->fold_seg = std::atoll(v);
-  if (const char* v = std::getenv("SR_AMD_HOST_REDUCE")) ctx->host_reduce = std::atoll(v);
-  if (const char* v = std::getenv("SR_AMD_STRESS_PROBE")) ctx->stress_probe = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_CODE_CACHE")) ctx->code_cache = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_FUSED_REDUCE")) ctx->fused_reduce = std::atoll(v);
-  if (const char* v = std::getenv("SR_AMD_GRAD_ROWS")) ctx->grad_rows_force = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_GRAD_SORT")) ctx->grad_sort = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_VSTK_ROWS")) ctx->vstk_rows = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_FIRST_CHUNK")) ctx->first_chunk = std::max(2, std::atoi(v));
-  if (const char* v = std::getenv("SR_AMD_CHUNK_MIN")) ctx->chunk_min = std::max<int64_t>(1, std::atoll(v));
-  if (const char* v = std::getenv("SR_AMD_HOST_IO")) ctx->host_io = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_EXACT_G")) ctx->exact_g = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_EXACT_W")) ctx->exact_w = std::atoi(v) == 1 ? 1 : 4;
-  if (const char* v = std::getenv("SR_AMD_EXACT_LIST_HOST")) ctx->exact_list_host = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_PAR_STAGE")) ctx->par_stage = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_DERIVED")) ctx->derived = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_MAX_ROW_BLOCKS")) ctx->max_row_blocks = std::max(1, std::atoi(v));
-  if (const char* v = std::getenv("SR_AMD_REF_FOLD")) ctx->ref_fold = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_FOLD_STORE_MB")) ctx->fold_store_mb = std::max<int64_t>(0, std::atoll(v));
-  if (const char* v = std::getenv("SR_AMD_FOLD_SLOT_MB")) ctx->fold_slot_mb = std::max<int64_t>(1, std::atoll(v));
-  if (const char* v = std::getenv("SR_AMD_FOLD_STATS")) ctx->fold_stats = std::atoi(v);
-  if (const char* v = std::getenv("SR_AMD_FOLD_DELTA_LOG2")) ctx->fold_delta_log2 = std::max(1, std::min(40, std::atoi(v)));
-  if (const char* v = std::getenv("SR_AMD_FOLD_SEG_MAX")) ctx->fold_seg_max = std::max<int64_t>(0, std::atoll(v));
-  if (const char* v = std::getenv("SR_AMD_FOLD_ROWS_MAX")) ctx->fold_rows_max = std::max<int64_t>(0, std::atoll(v));
-  if (const char* v = std::getenv("SR_AMD_FOLD_WALK_DBG")) ctx->fold_walk_dbg = std::atoi(v) & 6;
-  if (const char* v = std::getenv("SR_AMD_FOLD_REDUCE")) ctx->fold_reduce = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_FOLD_PRE_START")) ctx->fold_pre_start = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_FOLD_SINGLE_PASS")) ctx->fold_single_pass = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_FOLD_COMPACT")) ctx->fold_compact = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_FOLD_LIST_WGS"))
-    ctx->fold_list_wgs = std::max<int64_t>(0, std::min<int64_t>(std::atoll(v), kFoldListWgsMax));
-  if (const char* v = std::getenv("SR_AMD_LOSS_COMPACT")) ctx->loss_compact = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_LOSS_LIST_GROUPS")) ctx->loss_list_groups = std::max(0, std::atoi(v));
-  if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST")) ctx->fold_cand_est = std::atoi(v) != 0 ? 1 : 0;
-  if (const char* v = std::getenv("SR_AMD_FOLD_CAND_EST_MIN")) ctx->fold_cand_est_min = std::max(1, std::atoi(v));
-  if (const char* v = std::getenv("SR_AMD_TAIL_CHUNK")) ctx->tail_chunk = std::max(0, std::min(kTailTwelfths, std::atoi(v)));
-  if (const char* v = std::getenv("SR_AMD_EXACT_EARLY")) ctx->exact_early = std::atoi(v) != 0 ? 1 : 0;
+  sr_knobs_from_env(*ctx, [](const char* name) -> const char* { return std::getenv(name); });
   hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-  if (e == hipSuccess && std::getenv("SR_AMD_EAGER_STREAM2")) e = ctx->need_stream2();  // (A/B: the round-4 layout)
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_flags, hipEventDisableTiming);
-  for (int c = 0; c < kMaxChunks; ++c)
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_red[c], hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&ctx->ev_start);
-  if (e == hipSuccess) e = hipEventCreate(&ctx->ev_k0);
-  if (e == hipSuccess) e = hipEventCreate(&ctx->ev_k1);
-  if (e == hipSuccess) e = hipEventCreate(&ctx->ev_end);
-  if (e == hipSuccess) e = hipEventCreate(&ctx->ev_d0);
-  if (e == hipSuccess) e = hipEventCreate(&ctx->ev_d1);
-  for (int c = 0; c < kMaxChunks; ++c) {
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_c0[c]);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_c1[c]);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_fc0[c]);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_fc1[c]);
-  }
-  for (int b = 0; b < sr_ctx::kGradBuckets; ++b) {
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_g0[b]);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_g1[b]);
-  }
-  for (hipEvent_t& ev : ctx->ev_f)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
+  for_each_event(ctx, [&e](hipEvent_t& ev, bool timed) {
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, timed ? hipEventDefault : hipEventDisableTiming);
+  });
   if (e != hipSuccess) {
-    delete ctx;
+    destroy_ctx(ctx);
     return set_error(SR_ERR_HIP, std::string("stream/event creation: ") + hipGetErrorString(e));
   }
   *out = ctx;
@@ -4186,59 +4025,7 @@ int sr_init(int device, sr_ctx** out) {
 }
 
 int sr_shutdown(sr_ctx* ctx) {
-  if (!ctx) return SR_OK;
-  {
-    Lock l(ctx);
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->xport.reset();
-    if (ctx->hint.p == ctx->hint_reserve) {
-      ctx->hint.p = nullptr;
-      ctx->hint.cap = 0;
-    }
-    if (ctx->hint_reserve) (void)hipFree(ctx->hint_reserve);
-    ctx->hint_reserve = nullptr;
-    for (DevBuf* b : {&ctx->prog, &ctx->outs, &ctx->part_sum, &ctx->part_flag, &ctx->pred, &ctx->row_idx, &ctx->tree_list, &ctx->range_lo, &ctx->range_hi, &ctx->range_sums, &ctx->packed,
-                      &ctx->hint, &ctx->jsum_prog, &ctx->jsum_scratch, &ctx->probe_sum, &ctx->probe_flag, &ctx->g_code, &ctx->g_offsets, &ctx->g_consts, &ctx->g_const_off,
-                      &ctx->g_items, &ctx->g_part, &ctx->g_out, &ctx->derived_cols, &ctx->probe_derived, &ctx->coll_buf, &ctx->coll_packed, &ctx->ctl, &ctx->fold_io, &ctx->group_cnt,
-                      &ctx->fold_code, &ctx->fold_tab, &ctx->fold_store, &ctx->fold_ctl, &ctx->fold_io2, &ctx->fold_sq,
-                      &ctx->fold_tab2, &ctx->ptab, &ctx->fold_cand, &ctx->fold_list, &ctx->fold_wg, &ctx->fold_est, &ctx->loss_list})
-      b->release();
-    for (HostBuf* b : {&ctx->h_prog, &ctx->h_outs, &ctx->h_grad, &ctx->h_coll, &ctx->h_part, &ctx->h_exact, &ctx->h_ptab})
-      b->release();
-    for (sr_ctx::LossExpr& e : ctx->loss_exprs) {
-      if (e.dev) (void)hipFree(e.dev);
-      e.dev = nullptr;
-    }
-    for (int c = 0; c < kMaxChunks; ++c) {
-      (void)hipEventDestroy(ctx->ev_c0[c]);
-      (void)hipEventDestroy(ctx->ev_c1[c]);
-      (void)hipEventDestroy(ctx->ev_fc0[c]);
-      (void)hipEventDestroy(ctx->ev_fc1[c]);
-    }
-    for (int b = 0; b < sr_ctx::kGradBuckets; ++b) {
-      (void)hipEventDestroy(ctx->ev_g0[b]);
-      (void)hipEventDestroy(ctx->ev_g1[b]);
-    }
-    for (hipEvent_t ev : ctx->ev_f) (void)hipEventDestroy(ev);
-    if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-    if (ctx->stream3) {
-      (void)hipStreamSynchronize(ctx->stream3);
-      (void)hipStreamDestroy(ctx->stream3);
-    }
-    (void)hipEventDestroy(ctx->ev_flags);
-    for (int c = 0; c < kMaxChunks; ++c) (void)hipEventDestroy(ctx->ev_red[c]);
-    (void)hipEventDestroy(ctx->ev_join);
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    (void)hipEventDestroy(ctx->ev_start);
-    (void)hipEventDestroy(ctx->ev_k0);
-    (void)hipEventDestroy(ctx->ev_k1);
-    (void)hipEventDestroy(ctx->ev_end);
-    (void)hipEventDestroy(ctx->ev_d0);
-    (void)hipEventDestroy(ctx->ev_d1);
-    (void)hipStreamDestroy(ctx->stream);
-  }
-  delete ctx;
+  if (ctx) destroy_ctx(ctx);
   return SR_OK;
 }
 
@@ -5163,182 +4950,8 @@ int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value) {
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
   if (!name) return set_error(SR_ERR_INVALID_ARG, "tuning knob name is NULL");
   Lock l(ctx);
-  if (std::strcmp(name, "derived") == 0) {
-    ctx->derived = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "grad_lane_bins") == 0) {  // parametric gradients: per-lane class accumulators where they fit
-    ctx->grad_lane_bins = value != 0 ? 1 : 0;       // (0: the masked wave sums everywhere; the two differ in rounding)
-    return SR_OK;
-  }
-  if (std::strcmp(name, "grad_sort") == 0) {  // gradient work items ordered by program cost (SR_AMD_GRAD_SORT)
-    ctx->grad_sort = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "chunk_min") == 0) {  // the two-chunk pipeline's smallest first chunk (SR_AMD_CHUNK_MIN)
-    ctx->chunk_min = std::max<int64_t>(1, value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "first_chunk") == 0) {  // the two-chunk pipeline's first chunk is 1/value (SR_AMD_FIRST_CHUNK)
-    ctx->first_chunk = int(std::max<int64_t>(2, std::min<int64_t>(64, value)));
-    return SR_OK;
-  }
-  if (std::strcmp(name, "max_row_blocks") == 0) {  // row blocks per tree of a LOSS launch (SR_AMD_MAX_ROW_BLOCKS)
-    ctx->max_row_blocks = int(std::max<int64_t>(1, std::min<int64_t>(value, 1 << 16)));
-    return SR_OK;
-  }
-  if (std::strcmp(name, "probe") == 0) {  // dead-tree probe mode (SR_AMD_PROBE)
-    ctx->probe = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "host_io") == 0) {  // small-call results written to pinned memory (SR_AMD_HOST_IO: 0, 1)
-    if (value < 0 || value > 1) return set_error(SR_ERR_INVALID_ARG, "host_io must be 0 or 1");
-    ctx->host_io = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "vstk_rows") == 0) {  // register-stack rows per lane (SR_AMD_VSTK_ROWS; 0: default)
-    ctx->vstk_rows = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "grad_rows") == 0) {  // gradient kernel rows per lane (SR_AMD_GRAD_ROWS; 0: automatic)
-    ctx->grad_rows_force = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "host_reduce") == 0) {  // largest call (trees x row blocks) reduced on the host (SR_AMD_HOST_REDUCE)
-    ctx->host_reduce = value < 0 ? 0 : value;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fused_reduce") == 0) {  // in-launch partial reduction bound (SR_AMD_FUSED_REDUCE)
-    ctx->fused_reduce = value;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "ref_fold") == 0) {  // every complete tree's loss = the in-order fold (SR_AMD_REF_FOLD)
-    ctx->ref_fold = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_store_mb") == 0) {  // small calls: stored losses up to this size (SR_AMD_FOLD_STORE_MB)
-    ctx->fold_store_mb = value < 0 ? 0 : value;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_slot_mb") == 0) {  // FOLD mode: slow-segment slots (SR_AMD_FOLD_SLOT_MB)
-    ctx->fold_slot_mb = value < 1 ? 1 : value;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_single_pass") == 0) {  // candidate binades in the loss launch (SR_AMD_FOLD_SINGLE_PASS)
-    ctx->fold_single_pass = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_compact") == 0) {  // the FOLD pass over per-row-block work lists (SR_AMD_FOLD_COMPACT)
-    ctx->fold_compact = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "trees_per_block") == 0) {  // every grid's trees per workgroup, 0 = heuristic (SR_AMD_TREES_PER_BLOCK)
-    if (value < 0 || value > 256) return set_error(SR_ERR_INVALID_ARG, "trees_per_block: 0, or 1..256 (4 waves of 64 slots)");
-    ctx->tree_group = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_list_wgs") == 0) {  // the live workgroups a compacted FOLD launch aims for (SR_AMD_FOLD_LIST_WGS)
-    ctx->fold_list_wgs = std::max<int64_t>(0, std::min<int64_t>(value, kFoldListWgsMax));
-    return SR_OK;
-  }
-  if (std::strcmp(name, "loss_compact") == 0) {  // the loss launch over the positions the probe left alive (SR_AMD_LOSS_COMPACT)
-    ctx->loss_compact = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "loss_list_groups") == 0) {  // the tree groups a listed launch deals its list over (SR_AMD_LOSS_LIST_GROUPS)
-    ctx->loss_list_groups = int(std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)));
-    return SR_OK;
-  }
-  if (std::strcmp(name, "tail_chunk") == 0) {  // the last of three chunks of a plain path-2 call, in twelfths (SR_AMD_TAIL_CHUNK)
-    if (value < 0 || value > kTailTwelfths) return set_error(SR_ERR_INVALID_ARG, "tail_chunk: 0, or the last chunk's twelfths 1..6");
-    ctx->tail_chunk = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "exact_early") == 0) {  // the exact-sum pass beside the last fold chains (SR_AMD_EXACT_EARLY)
-    ctx->exact_early = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_cand_est") == 0) {  // the candidates' guess from the running prefix (SR_AMD_FOLD_CAND_EST)
-    ctx->fold_cand_est = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_cand_est_min") == 0) {  // finished row blocks that make it usable (SR_AMD_FOLD_CAND_EST_MIN)
-    ctx->fold_cand_est_min = int(value < 1 ? 1 : (value > (1 << 30) ? (1 << 30) : value));
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_debug_fail") == 0) {  // tests: trees t % value == 0 take the fold's fallback
-    ctx->fold_debug_fail = int(value < 0 ? 0 : value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_delta_log2") == 0) {  // the plan's window 2^-value around the f64 prefix
-    ctx->fold_delta_log2 = int(value < 1 ? 1 : (value > 40 ? 40 : value));
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_seg_max") == 0) {  // longest row block folded (SR_AMD_FOLD_SEG_MAX)
-    ctx->fold_seg_max = value < 0 ? 0 : value;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_rows_max") == 0) {  // longest fold (SR_AMD_FOLD_ROWS_MAX)
-    ctx->fold_rows_max = value < 0 ? 0 : value;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "fold_seg") == 0) {  // rows per segment of the in-order loss fold (SR_AMD_FOLD_SEG)
-    ctx->fold_seg = value < 0 ? -1 : value;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "exact_w") == 0) {  // waves per workgroup of the EXACT pass (SR_AMD_EXACT_W)
-    ctx->exact_w = value == 1 ? 1 : 4;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "exact_g") == 0) {  // listed trees per EXACT workgroup, 0 = heuristic (SR_AMD_EXACT_G)
-    ctx->exact_g = int(value < 0 ? 0 : (value > 64 ? 64 : value));
-    return SR_OK;
-  }
-  if (std::strcmp(name, "code_cache") == 0) {  // LDS program cache (SR_AMD_CODE_CACHE)
-    ctx->code_cache = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "timing") == 0) {  // 0: record no timing events (kernel times read as 0)
-    ctx->timing = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "stress_probe") == 0) {  // the probe over the stress rows (SR_AMD_STRESS_PROBE)
-    ctx->stress_probe = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "rows_per_lane") == 0) {  // kernel build per call (SR_AMD_ROWS_PER_LANE; 0 = default)
-    ctx->rows_override = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "balance") == 0) {  // launch order dealt over tree groups (SR_AMD_BALANCE)
-    ctx->balance_groups = value != 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "debug_hint_regrow") == 0) {  // tests: hint-array growth in place, stale epochs in it
-    ctx->debug_hint_regrow = value != 0 ? 1 : 0;
-    return SR_OK;
-  }
-  if (std::strcmp(name, "inject_failure_post") == 0) {
-    ctx->inject_post = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "inject_failure_post_exact") == 0) {
-    ctx->inject_post_exact = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "inject_failure_post_wsum") == 0) {  // tests: this rank's copy of the k-th Σw gather fails
-    ctx->inject_post_wsum = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "inject_failure_post_gather") == 0) {
-    ctx->inject_post_gather = int(value);
-    return SR_OK;
-  }
-  if (std::strcmp(name, "inject_failure") == 0) {  // tests: the next `value` collective-buffer growths fail
-    ctx->inject_fail = int(value);
-    return SR_OK;
-  }
-  return set_error(SR_ERR_INVALID_ARG, std::string("unknown tuning knob '") + name + "'");
+  std::string err;
+  return sr_knob_set(*ctx, name, value, &err) == 0 ? SR_OK : set_error(SR_ERR_INVALID_ARG, err);
 }
 
 int sr_last_grad_info(sr_ctx* ctx, int n, double* kernel_ms, double* flops, int64_t* items, int* rows_per_lane) {

@@ -78,7 +78,7 @@ class DeviceContext:
 
     def set_tuning(self, name, value):
         """Run-time tuning knob (include/sr_amd.h lists them): "derived", "probe", "stress_probe",
-        "code_cache", "timing", "rows_per_lane", "balance", "fused_reduce", "exact_w", "exact_g", "fold_seg",
+        "code_cache", "timing", "rows_per_lane", "balance", "exact_w", "exact_g", "fold_seg",
         "ref_fold" (the in-order loss fold: 1 default, 0 the f64 sums), "fold_seg_max" / "fold_rows_max"
         (the longest row block / fold folded: past them a call keeps the f64 sums — these three are the
         knobs results depend on), "fold_store_mb", "fold_slot_mb", "fold_delta_log2", "fold_single_pass" (the

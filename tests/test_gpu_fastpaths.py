@@ -198,8 +198,7 @@ def test_probe_modes_change_nothing(dtype):
 @pytest.mark.parametrize("dtype,n_rows,n_trees", [(np.float32, 100_000, 31), (np.float64, 100, 40), (np.float32, 3000, 300)])
 def test_small_call_latency_options_change_nothing(dtype, n_rows, n_trees):
     """The search's call shapes under the latency options: results written by the kernel into pinned
-    host memory ("host_io"), the partial reduction in the launch ("fused_reduce"), in a separate launch
-    or on the host from partials the kernel wrote into pinned memory ("host_reduce"): losses and flags
+    host memory ("host_io"), the partial reduction in a separate launch or on the host from partials the kernel wrote into pinned memory ("host_reduce"): losses and flags
     bit for bit equal — with the in-order fold ("ref_fold" 1, the default, which keeps the partials on
     the device) and with the f64 sums ("ref_fold" 0)."""
     import sr_amd
@@ -216,15 +215,13 @@ def test_small_call_latency_options_change_nothing(dtype, n_rows, n_trees):
         res = []
         try:
             ctx.set_tuning("ref_fold", ref_fold)
-            for host_io, fused, hred in ((1, 1 << 30, 0), (1, 0, 0), (0, 0, 0), (1, 0, 1 << 20), (0, 0, 1 << 20)):
+            for host_io, hred in ((1, 0), (0, 0), (1, 1 << 20), (0, 1 << 20)):
                 ctx.set_tuning("host_io", host_io)
-                ctx.set_tuning("fused_reduce", fused)
                 ctx.set_tuning("host_reduce", hred)
                 res.append(eval_loss_batch(tb, ds, opts))
         finally:
             ctx.set_tuning("ref_fold", 1)
             ctx.set_tuning("host_io", 1)
-            ctx.set_tuning("fused_reduce", 0)
             ctx.set_tuning("host_reduce", 8192)
         l0, c0 = res[0]
         assert c0.mean() > 0.2
