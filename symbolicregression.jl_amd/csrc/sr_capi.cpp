@@ -153,9 +153,7 @@ struct sr_ctx : SrKnobs {
   hipError_t need_stream2() {
     return stream2 ? hipSuccess : hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking);
   }
-  // (the exact_early knob's state, sr_knobs.h)
-  bool want_early = false;  // set by eval_loss_submit around its run_batch
-  bool early_last = false;  // the last run_batch copied the flags early (and left the results' copy to the caller)
+  // (the exact_early knob's events and stream, sr_knobs.h)
   hipEvent_t ev_flags = nullptr;
   hipEvent_t ev_red[kMaxChunks] = {};  // chunk c's loss launches and reduces have ended
   hipStream_t stream3 = nullptr;       // the early exact-sum pass's, created on the first such call
@@ -178,9 +176,33 @@ struct sr_ctx : SrKnobs {
   double grad_flops[kGradBuckets] = {};
   int64_t grad_items[kGradBuckets] = {};
   int grad_rows[kGradBuckets] = {};
-  int n_chunks_last = 0;
-  bool derived_last = false;  // the last run_batch launched derived columns (timed by ev_d0/ev_d1)
-  int n_derived_last = 0;
+  // What the last run_batch did, for the sr_last_* / sr_tuning_info / sr_ref_fold_info / sr_last_fold_cand
+  // getters and settle_timing: no call decides anything from an earlier call's record.  Written by a call's own
+  // run_batch (and its fold's launches); the fold's internal prediction passes (BatchWants::internal) write a
+  // scratch copy instead.
+  struct LastCall {
+    int n_chunks = 0;
+    int rows = 0;          // rows per lane of the interpreter launches (sr_last_phase_ms out[7])
+    bool timed = false;    // the call recorded its events
+    bool derived = false;  // it launched derived columns (timed by ev_d0 / ev_d1)
+    int n_derived = 0;
+    int fold_path = 0;     // 0 none, 1 stored losses, 2 FOLD mode
+    bool fold_timed = false;
+    // the listed launches (loss_compact): per chunk the launch's positions (0: not listed), and the counters
+    // read back once on request (sr_last_phase_ms out[16..18])
+    int64_t loss_listed_np[kMaxChunks] = {};
+    int64_t loss_list_nt = 0;
+    bool loss_list_read = true;
+    int64_t n_loss_listed_launches = 0, n_loss_live = 0, n_loss_excl = 0;
+    // the compacted FOLD launches (fold_compact): per region its row blocks (0: none) and the call's row
+    // blocks per position, for sr_last_phase_ms out[19..] (read back once on request)
+    int fold_wg_nrb[2 * kMaxChunks] = {};
+    int64_t fold_wg_stride_rb = 0;
+    bool fold_wg_read = true;
+    double fold_wg_info[2 * kMaxChunks][4] = {};  // {live workgroups, listed entries, g, the longest list}
+    bool fold_cand_read = true;  // fold_ctl's counters are in n_cand_* below
+    int64_t n_cand_taken = 0, n_cand_rerun = 0;
+  } last;
   int64_t n_exact_last = 0;  // trees of the last eval_loss call sent through the exact-sum pass
   int64_t n_fold_last = 0;   // trees of the last eval_loss call whose loss fold was computed in order (sr_fold.h)
   int64_t fold_slow_last = 0;  // ... their segments folded row by row (the rest: composed steps)
@@ -210,8 +232,6 @@ struct sr_ctx : SrKnobs {
   double* d_out_sum = nullptr;
   uint32_t* d_out_flag = nullptr;
   size_t outs_flag_off = 0;
-  bool want_host_out = false;  // (host_io) set by eval_loss_impl around its run_batch
-  bool outs_on_host = false;   // the last run_batch wrote {Σ, flags} to h_outs
   uint32_t hint_epoch = 0;  // dead-tree hint epoch of the current call
   void* hint_reserve = nullptr;    // debug_hint_regrow's fixed-address reservation
   std::mutex mu;
@@ -269,7 +289,6 @@ struct sr_ctx : SrKnobs {
   // the two above are read from the last call's events lazily, when asked for (sr_last_kernel_ms /
   // sr_last_phase_ms): a small call (the search's) does not pay the event queries it never reads
   bool timing_pending = false;
-  bool timed_last = false;  // the last run_batch recorded its events
   // host-side phases of the last eval_loss call (ms): compile, upload+launch, wait, exact pass,
   // finalize (sr_last_phase_ms)
   double phase_ms[5] = {0, 0, 0, 0, 0};
@@ -278,52 +297,27 @@ struct sr_ctx : SrKnobs {
     phase_t = t;
     for (double& v : phase_ms) v = 0.0;
   }
-  bool internal_pass = false;  // the fold's PRED passes: run_batch leaves the call's phase clock alone
   void mark_phase(int i) {
-    if (internal_pass) return;
     const auto now = std::chrono::steady_clock::now();
     phase_ms[i] = std::chrono::duration<double, std::milli>(now - phase_t).count();
     phase_t = now;
   }
   int cu_count = 256;
-  int rows_last = 0;        // rows per lane of the last interpreter call (sr_last_phase_ms out[7])
   std::vector<uint32_t> perm_host;
-  // The in-order loss fold's buffers and last-call records (the ref_fold and fold_* knobs: sr_knobs.h)
+  // The in-order loss fold's buffers (the ref_fold and fold_* knobs: sr_knobs.h)
   DevBuf fold_cand;          // (fold_single_pass) the candidates, [row block][position] int4 (sr_fold_dev.h)
   DevBuf fold_list;          // (fold_compact) [row block][position] int32, laid out as the partials
   DevBuf fold_wg;            // per region (2 per chunk): {cnt [n_rb], wg0 [n_rb + 1], g}
-  // the last call's compacted FOLD launches: per region its row blocks (0: none) and the call's row blocks per
-  // position, for sr_last_phase_ms out[19..] (read back once on request)
-  int fold_wg_nrb[2 * kMaxChunks] = {};
-  int64_t fold_wg_stride_rb = 0;
-  bool fold_wg_read = true;
-  double fold_wg_info[2 * kMaxChunks][4] = {};  // {live workgroups, listed entries, g, the longest list}
   DevBuf loss_list;          // (loss_compact) {list int32 [nt] | cnt int32 [kMaxChunks][4] | excl uint8 [nt]} (sr_plan.h)
-  // the last call's listed launches: per chunk the launch's positions (0: not listed), and the counters read
-  // back once on request (sr_last_phase_ms out[16..18])
-  int64_t loss_listed_np[kMaxChunks] = {0, 0, 0, 0};
-  int64_t loss_list_nt_last = 0;
-  bool loss_list_read = true;
-  int64_t n_loss_listed_launches_last = 0, n_loss_live_last = 0, n_loss_excl_last = 0;
   DevBuf fold_est;           // (fold_cand_est) per launch position: {f64 sum [nt] | u32 count [nt]}, zeroed by every call
-  bool fold_cand_read = true;  // fold_ctl's counters of the last call are in n_cand_* below
-  int64_t n_cand_taken_last = 0, n_cand_rerun_last = 0;
   DevBuf fold_dbg;           // (fold_stats)
-  bool want_fold = false;    // set by eval_loss_submit around its run_batch
-  int fold_path_last = 0;    // 0 none, 1 stored losses, 2 FOLD mode
   DevBuf fold_code, fold_tab, fold_store, fold_ctl, fold_io2, fold_sq, fold_tab2;
   std::shared_ptr<void> fold_job;  // a row-sharded call's FoldJob<T>, until its ranks agree on the verdicts
   size_t outs_fval_off = 0, outs_fst_off = 0, outs_bytes_all = 0;
   hipEvent_t ev_fc0[kMaxChunks] = {}, ev_fc1[kMaxChunks] = {};  // each chunk's fold launches
-  bool fold_timed_last = false;
   int64_t n_ref_ok_last = 0, n_ref_fail_last = 0;  // trees whose loss is the walk's fold / that fell back
   double fold_kernel_ms_last = 0.0;
-  // A parametric call (sr_eval_*_parametric): the parameter side of the batch the running call scores,
-  // set by the entry point for the call's duration (under the context's lock); run_batch and the
-  // exact-sum pass then compile parameter leaves, upload the table and launch the PARAM kernels.  The
-  // fold's prediction passes over a few trees of the batch swap in those trees' side (fold_prepare).
-  const sr_param_batch* param = nullptr;
-  DevBuf ptab;     // the last parametric run_batch's table, [tree][parameter][class] (T)
+  DevBuf ptab;     // the last parametric run_batch's table (EvalReq::params), [tree][parameter][class] (T)
   HostBuf h_ptab;  // its pinned staging
 };
 
@@ -445,6 +439,50 @@ struct ViewSpec {
   const int32_t* tree_view;
   int n_views;
   int64_t view_len;
+};
+
+// What a scoring call asked for: filled once by the entry point and passed by reference to every function
+// behind it (the fold's fallback builds a sub-request over a few of its trees: fold_prepare).
+struct EvalReq {
+  const sr_dataset* ds = nullptr;
+  int opset_id = 0;
+  const sr_tree_batch* trees = nullptr;
+  const sr_param_batch* params = nullptr;  // the batch's parameter side (sr_eval_*_parametric); NULL: plain trees
+  const int64_t* row_idx = nullptr;        // the view's rows (views: n_views views of n_idx rows each); NULL: every row
+  int64_t n_idx = 0;
+  const ViewSpec* views = nullptr;         // several row views in one call; NULL: one view
+  int loss_kind = 0;                       // as passed to the eval calls (decode_loss)
+  bool gather() const { return row_idx != nullptr && n_idx > 0; }
+  int64_t n_eval() const { return gather() ? n_idx : ds->n; }
+  // view v alone, as a request of its own (the exact-sum pass and the fallback fold run view by view)
+  EvalReq view(int v) const {
+    EvalReq r = *this;
+    r.row_idx = gather() ? row_idx + int64_t(v) * n_idx : nullptr;
+    r.views = nullptr;
+    return r;
+  }
+};
+
+// What a caller wants from run_batch beside the request.
+struct BatchWants {
+  int mode = SR_MODE_LOSS;
+  int64_t n_total = 0;          // rows of the whole view over every shard (the overflow budgets)
+  bool allow_derived = false;   // derived columns may be used
+  const ShardCtl* shard = nullptr;
+  bool host_out = false;        // (host_io) a small call's {Σ, flags} may go straight to pinned memory
+  bool fold = false;            // the caller takes every complete tree's in-order fold (ref_fold)
+  bool early = false;           // the caller can take the flags early (exact_early)
+  bool takes_expr = false;      // the call accepts expression losses
+  bool internal = false;        // a pass inside another call (the fold's PRED passes): the last-call record, the
+                                // timing events and the phase clock stay that call's
+};
+
+// What run_batch hands back beside the context-owned buffers (d_out_sum, d_out_flag, ...).
+struct BatchResult {
+  Grid grid;                  // the last launch's
+  bool early = false;         // the flags were copied early, the results' copy is left to the caller
+  bool outs_on_host = false;  // {Σ, flags} are in h_outs already
+  int fold_path = 0;          // 0 none, 1 stored losses, 2 FOLD mode
 };
 
 // Rows of the reference's loss fold for the overflow rule (sr_fold.h), or 0 when the rule does not
@@ -574,11 +612,9 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
     int32_t* list = ctx->fold_list.as<int32_t>() + fr.off(job.n_rb);
     SR_HIP_CHECK(sr_launch_fold_compact(ft, np, nrb, fr.a.trees_per_block, int(ctx->fold_list_wgs),
                                         int(std::min<int64_t>(fr.n_blocks, kFoldListWgsMax)), list, cnt, wg0, cs));
-    if (!ctx->internal_pass) {  // (sr_last_phase_ms out[19..])
-      ctx->fold_wg_nrb[fr.idx] = nrb;
-      ctx->fold_wg_stride_rb = job.n_rb;
-      ctx->fold_wg_read = false;
-    }
+    ctx->last.fold_wg_nrb[fr.idx] = nrb;  // (sr_last_phase_ms out[19..]; no internal pass folds)
+    ctx->last.fold_wg_stride_rb = job.n_rb;
+    ctx->last.fold_wg_read = false;
     fa.fold_list = list;
     fa.fold_cnt = cnt;
     fa.fold_wg0 = wg0;
@@ -651,18 +687,21 @@ struct BatchChunk {
 // One call's state, written by the stages in order, and the stages (run() calls them).
 template <typename T>
 struct BatchCall {
-  // the inputs
+  // the inputs: the request, what the caller wants, and where the merged program summary and the results go
   sr_ctx* ctx;
-  const sr_dataset* ds;
-  int opset_id;
-  const sr_tree_batch* trees;
-  const int64_t* row_idx;
-  int64_t n_idx, n_total;
-  int loss_kind, mode;
+  const EvalReq& req;
+  const BatchWants& want;
   SrProgramBatch<T>* prog;
-  bool allow_derived;
-  const ShardCtl* shard;
-  const ViewSpec* views;
+  BatchResult* res;
+  // the last-call record this run writes: the context's, or — an internal pass — a scratch copy
+  sr_ctx::LastCall scratch;
+  sr_ctx::LastCall& last;
+  bool allow_derived;  // (want.allow_derived until a stage withdraws it: several views, an expression loss, parameters)
+  BatchCall(sr_ctx* c, const EvalReq& q, const BatchWants& w, SrProgramBatch<T>* p, BatchResult* r)
+      : ctx(c), req(q), want(w), prog(p), res(r), last(w.internal ? scratch : c->last), allow_derived(w.allow_derived) {}
+  void mark_phase(int i) {
+    if (!want.internal) ctx->mark_phase(i);
+  }
   // validate_call: the view, the decoded loss, the batch's size
   bool gather = false, multi = false;
   int64_t n_eval = 0, n_rows_up = 0, nt = 0, total_nodes = 0;
@@ -680,7 +719,7 @@ struct BatchCall {
   int tier = 0, R = 0, W = 0, Rv = 0, n_rb = 1, n_chunks = 1;
   GridSpec gs;
   Grid g_ls, g_vs;  // the whole batch's grids at R (depth 1) and, Rv > 0, at Rv (depth 0)
-  Grid glast;       // the last launch's (the callers' grid_out)
+  Grid glast;       // the last launch's (BatchResult::grid)
   // bind_buffers: the staging image's layout, its device and pinned copies, the partials' count
   ProgImage img;
   size_t n_part = 0;
@@ -715,62 +754,56 @@ struct BatchCall {
   // the largest leaf value of the call, as the deferred checks bound it
   double leaf_bound(double max_abs_x_data) const { return parametric ? std::max(max_abs_x_data, max_abs_p) : max_abs_x_data; }
   // Σ over n_total rows of values below tbig cannot overflow T, even with rounding slack.
-  T tbig() const { return T(t_max<T>() / (2.0 * double(n_total > 0 ? n_total : 1))); }
+  T tbig() const { return T(t_max<T>() / (2.0 * double(want.n_total > 0 ? want.n_total : 1))); }
 
   // The view, the row-block bound, the loss and the batch's size.
   int validate_call() {
-    gather = row_idx != nullptr && n_idx > 0;
+    gather = req.gather();
     // PRED passes (the fold's few band trees) write no partials: more row blocks fill the GPU (C4's 14 trees
     // x 2^26 rows ran 1,024 workgroups at 256)
-    mrb = mode == SR_MODE_PRED ? std::max(ctx->max_row_blocks, 4096) : ctx->max_row_blocks;
-    n_eval = gather ? n_idx : ds->n;
+    mrb = want.mode == SR_MODE_PRED ? std::max(ctx->max_row_blocks, 4096) : ctx->max_row_blocks;
+    n_eval = req.n_eval();
     if (n_eval <= 0) return set_error(SR_ERR_INVALID_ARG, "no rows to evaluate");
     // under the in-order fold, row blocks of at most fold_seg_max rows on the largest shard (every rank
     // the same count): a slow block's rows are kept whole (C4's 2^26 rows per GPU: 4,096 blocks of 16k)
-    if (mode == SR_MODE_LOSS && ctx->want_fold && ctx->ref_fold && sizeof(T) == 4 && ctx->fold_seg_max > 0 &&
-        (shard ? n_total : n_eval) <= ctx->fold_rows_max) {
-      const int64_t max_rows = shard ? sr_max_shard_rows(ds->shard_offs, n_eval) : n_eval;
+    if (want.mode == SR_MODE_LOSS && want.fold && ctx->ref_fold && sizeof(T) == 4 && ctx->fold_seg_max > 0 &&
+        (want.shard ? want.n_total : n_eval) <= ctx->fold_rows_max) {
+      const int64_t max_rows = want.shard ? sr_max_shard_rows(req.ds->shard_offs, n_eval) : n_eval;
       const int64_t need = (max_rows + ctx->fold_seg_max - 1) / ctx->fold_seg_max;
       if (need > mrb) mrb = int(std::min<int64_t>(need, 16384));
     }
     // several views: one launch, its tree groups view-pure (SrSegment); rows uploaded for every view
-    multi = views != nullptr && gather && mode == SR_MODE_LOSS;
-    n_rows_up = multi ? int64_t(views->n_views) * n_idx : n_idx;
+    multi = req.views != nullptr && gather && want.mode == SR_MODE_LOSS;
+    n_rows_up = multi ? int64_t(req.views->n_views) * req.n_idx : req.n_idx;
     if (multi) allow_derived = false;
-    // (expression losses: plain single-context LOSS calls only — the sharded, partials and parametric calls
-    //  pass no slot and are refused with the message that names the restriction)
-    const bool takes_expr = mode == SR_MODE_LOSS && !shard && ctx->param == nullptr && ctx->want_host_out;
-    if (decode_loss(ctx, loss_kind, &lkind, &lparam, takes_expr ? &lexpr : nullptr) != SR_OK) return SR_ERR_INVALID_ARG;
-    if (check_loss_expr_weights(lexpr, ds) != SR_OK) return SR_ERR_INVALID_ARG;
+    // (expression losses: the calls that ask for them, BatchWants::takes_expr — plain single-context LOSS calls;
+    //  the sharded, partials and parametric calls pass no slot and are refused with the message that names the
+    //  restriction)
+    if (decode_loss(ctx, req.loss_kind, &lkind, &lparam, want.takes_expr ? &lexpr : nullptr) != SR_OK)
+      return SR_ERR_INVALID_ARG;
+    if (check_loss_expr_weights(lexpr, req.ds) != SR_OK) return SR_ERR_INVALID_ARG;
     if (lexpr) allow_derived = false;  // (derived columns are chosen for the catalog builds: not measured here)
-    nt = trees->n_trees;
+    nt = req.trees->n_trees;
     if (nt < 0) return set_error(SR_ERR_INVALID_ARG, "negative tree count");
-    if (nt > 0 && !trees->offsets) return set_error(SR_ERR_INVALID_ARG, "sr_tree_batch has NULL arrays");
-    total_nodes = nt > 0 ? trees->offsets[nt] - trees->offsets[0] : 0;
+    if (nt > 0 && !req.trees->offsets) return set_error(SR_ERR_INVALID_ARG, "sr_tree_batch has NULL arrays");
+    total_nodes = nt > 0 ? req.trees->offsets[nt] - req.trees->offsets[0] : 0;
     if (total_nodes < 0 || total_nodes > int64_t(0xffffffffu) / 2)
       return set_error(SR_ERR_INVALID_ARG, "tree batch node count out of range");
     return SR_OK;
   }
 
-  // A parametric call (sr_ctx::param): the table the kernels gather from, [tree][parameter][class] in T
-  // (each tree's Julia column-major matrix transposed, so that one parameter's classes are contiguous),
+  // A parametric call (EvalReq::params; the entry point has checked the batch against the dataset: check_params):
+  // the table the kernels gather from, [tree][parameter][class] in T (each tree's Julia column-major matrix
+  // transposed, so that one parameter's classes are contiguous),
   // staged in pinned memory here and uploaded by begin_programs; the leaf bound of the deferred checks
   // becomes max(max|X|, max|P|), Inf when any entry is non-finite (then, as for such data, the
   // per-node-check tier runs: DESIGN.md §4.6).  nfk: the X rows a launch stages (the hidden class row
   // included).
   int stage_param_table() {
-    pb = ctx->param;
+    pb = req.params;
     parametric = pb != nullptr;
-    nfk = int(ds->nf) + (parametric ? 1 : 0);
+    nfk = int(req.ds->nf) + (parametric ? 1 : 0);
     if (!parametric) return SR_OK;
-    if (shard) return set_error(SR_ERR_INVALID_ARG, "parametric trees are not supported by the sharded calls");
-    if (ds->n_classes <= 0) return set_error(SR_ERR_INVALID_ARG, "a parametric call needs a dataset uploaded with classes");
-    if (pb->n_classes != ds->n_classes)
-      return set_error(SR_ERR_INVALID_ARG, "sr_param_batch n_classes " + std::to_string(pb->n_classes) +
-                                               " differs from the dataset's " + std::to_string(ds->n_classes));
-    if (pb->max_parameters < 0 || pb->max_parameters > 65535) return set_error(SR_ERR_INVALID_ARG, "bad max_parameters");
-    if (nt > 0 && (!pb->is_parameter || !pb->parameter || (pb->max_parameters > 0 && !pb->parameters)))
-      return set_error(SR_ERR_INVALID_ARG, "sr_param_batch has NULL arrays");
     const int64_t K = pb->max_parameters, NC = pb->n_classes;
     p_stride = K * NC;
     if (p_stride > int64_t(INT_MAX)) return set_error(SR_ERR_INVALID_ARG, "parameter matrix too large");
@@ -801,12 +834,12 @@ struct BatchCall {
     // (SR_TRACK_LITE: the deferred-check kernels bound untracked values by L x max|x| for trees of up to
     //  L nodes; data at or above tbig / L — huge or non-finite values, never seen in practice — runs the
     //  per-node-check kernels instead, whose checks hold for any data)
-    tier = ctx->tiers[opset_id];
+    tier = ctx->tiers[req.opset_id];
 #ifdef SR_TRACK_LITE
-    if (tier == SR_TIER_BASIC && mode == SR_MODE_LOSS && nt > 0) {
+    if (tier == SR_TIER_BASIC && want.mode == SR_MODE_LOSS && nt > 0) {
       int64_t lmax = 1;
-      for (int64_t t = 0; t < nt; ++t) lmax = std::max<int64_t>(lmax, trees->offsets[t + 1] - trees->offsets[t]);
-      const double mx = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
+      for (int64_t t = 0; t < nt; ++t) lmax = std::max<int64_t>(lmax, req.trees->offsets[t + 1] - req.trees->offsets[t]);
+      const double mx = leaf_bound(want.shard ? want.shard->max_abs_x : req.ds->max_abs_x);
       if (!(mx < double(tbig()) / double(lmax))) tier = SR_TIER_FULL;
     }
 #endif
@@ -815,25 +848,25 @@ struct BatchCall {
     // (an expression-loss call's likewise, sr_launch_eval_lossx: the classic kernel at its default rows per
     //  lane, 4 waves, no register-stack build — the "rows_per_lane" / "waves" / register-stack knobs map onto it)
     const bool small_set = parametric || lexpr != nullptr;
-    R = sr_rows_per_lane<T>(mode, tier, small_set ? 0 : ctx->rows_override);
-    W = small_set ? 4 : sr_waves_per_block(int(sizeof(T)), mode, tier, R, ctx->waves_override);
+    R = sr_rows_per_lane<T>(want.mode, tier, small_set ? 0 : ctx->rows_override);
+    W = small_set ? 4 : sr_waves_per_block(int(sizeof(T)), want.mode, tier, R, ctx->waves_override);
     // register-stack kernel (f32 BASIC loss over the full dataset): Rv rows per lane, used for every
     // chunk whose programs need <= 2 operand-stack slots (all trees of <= 30 nodes); other chunks run
     // the LDS-stack kernel at R rows per lane
-    Rv = (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && !gather)
+    Rv = (want.mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && !gather)
                ? sr_vstk_rows(int(sizeof(T)), n_eval, ctx->vstk_rows ? ctx->vstk_rows : ctx->rows_override)
                : 0;
     if (parametric && Rv > 0) Rv = sizeof(T) == 4 ? 16 : 8;  // (the one register-stack build of a parametric call)
     if (lexpr) Rv = 0;
     // every grid of the call comes from this one spec
-    gs = GridSpec{int(sizeof(T)), n_eval, W, nfk, ds->w != nullptr, ctx->tree_group, mrb};
+    gs = GridSpec{int(sizeof(T)), n_eval, W, nfk, req.ds->w != nullptr, ctx->tree_group, mrb};
     // a wide dataset whose register-stack tile (its rows per lane are twice the classic kernel's) would
     // not fit the LDS runs the classic kernel instead (Float64 with ~40-75 features)
     if (Rv > 0) {
       g_vs = gs.grid(nt > 0 ? nt : 1, Rv, 0);
       if (g_vs.lds > kLdsMax) Rv = 0;
     }
-    ctx->rows_last = Rv > 0 ? Rv : R;  // (every C2-like tree fits the register stack)
+    last.rows = Rv > 0 ? Rv : R;  // (every C2-like tree fits the register stack)
     g_ls = gs.grid(nt > 0 ? nt : 1, R, 1);
     glast = g_ls;
     n_rb = g_ls.n_row_blocks;
@@ -844,7 +877,7 @@ struct BatchCall {
   // the next one is staged): a program has at most one instruction per node
   int bind_buffers() {
     s = ctx->stream;
-    img = sr_prog_image(total_nodes, nt, sizeof(SrIns<T>), multi ? size_t(views->n_views) : 0);
+    img = sr_prog_image(total_nodes, nt, sizeof(SrIns<T>), multi ? size_t(req.views->n_views) : 0);
     SR_HIP_CHECK(ctx->prog.ensure(img.bytes));
     SR_HIP_CHECK(ctx->h_prog.ensure(img.bytes, s, ctx->stream2));
     dprog = ctx->prog.as<char>();
@@ -864,14 +897,15 @@ struct BatchCall {
   // (a row-sharded call: the global rows and every shard's weights; its ranks fold or not together —
   //  the choice depends on the largest shard's rows, known to every rank)
   int plan_fold() {
-    fold_n_terms = shard ? ((ds->w && ds->shard_w_min < 0.0) ? 0 : n_total) : fold_terms(ds, n_eval, loss_kind);
-    if (shard) ctx->fold_job.reset();
-    if (ctx->want_fold && ctx->ref_fold && mode == SR_MODE_LOSS && nt > 0 && fold_n_terms > 0) {
+    fold_n_terms = want.shard ? ((req.ds->w && req.ds->shard_w_min < 0.0) ? 0 : want.n_total)
+                              : fold_terms(req.ds, n_eval, req.loss_kind);
+    if (want.shard) ctx->fold_job.reset();
+    if (want.fold && ctx->ref_fold && want.mode == SR_MODE_LOSS && nt > 0 && fold_n_terms > 0) {
       FoldPlanIn in;
       in.nt = nt;
       in.n_eval = n_eval;
-      in.max_shard = shard ? sr_max_shard_rows(ds->shard_offs, n_eval) : n_eval;
-      in.fold_len = shard ? n_total : n_eval;
+      in.max_shard = want.shard ? sr_max_shard_rows(req.ds->shard_offs, n_eval) : n_eval;
+      in.fold_len = want.shard ? want.n_total : n_eval;
       in.elem_size = int(sizeof(T));
       in.tier = tier;
       in.R = R;
@@ -909,36 +943,34 @@ struct BatchCall {
     }
     // the candidate-composing loss launch (sr_ctx::fold_single_pass): plain calls only
     fold_cand = fold.path == 2 && ctx->fold_single_pass && sizeof(T) == 4 && tier == SR_TIER_BASIC && !gather &&
-                !multi && !shard && ctx->param == nullptr && n_rb > 1;
+                !multi && !want.shard && !parametric && n_rb > 1;
     if (fold_cand) SR_HIP_CHECK(ctx->fold_cand.ensure(n_part * sizeof(int4) + 16));
     if (fold_cand && ctx->fold_cand_est) {  // every position's running prefix {sum | count}: none finished yet
       SR_HIP_CHECK(ctx->fold_est.ensure(size_t(nt) * (sizeof(double) + sizeof(uint32_t)) + 8));
       SR_HIP_CHECK(hipMemsetAsync(ctx->fold_est.p, 0, size_t(nt) * (sizeof(double) + sizeof(uint32_t)), s));
     }
     // the compacted FOLD launch (sr_ctx::fold_compact): plain calls only
-    fold_compact = fold.path == 2 && ctx->fold_compact && !gather && !multi && !shard && ctx->param == nullptr;
+    fold_compact = fold.path == 2 && ctx->fold_compact && !gather && !multi && !want.shard && !parametric;
     if (fold_compact) {
       SR_HIP_CHECK(ctx->fold_list.ensure(n_part * sizeof(int32_t) + 4));
       SR_HIP_CHECK(ctx->fold_wg.ensure(sr_fold_wg_words(n_rb) * sizeof(int32_t)));
     }
     // the listed loss launch (sr_ctx::loss_compact): the calls that take both of the above
-    loss_compact = fold_compact && fold_cand && ctx->loss_compact && mode == SR_MODE_LOSS;
+    loss_compact = fold_compact && fold_cand && ctx->loss_compact && want.mode == SR_MODE_LOSS;
     if (loss_compact) SR_HIP_CHECK(ctx->loss_list.ensure(sr_loss_list_bytes(nt)));
-    if (!ctx->internal_pass) {  // (the fallback's prediction passes leave the call's record alone)
-      for (int c = 0; c < kMaxChunks; ++c) ctx->loss_listed_np[c] = 0;
-      ctx->loss_list_nt_last = nt;
-      ctx->loss_list_read = true;
-      ctx->n_loss_listed_launches_last = ctx->n_loss_live_last = ctx->n_loss_excl_last = 0;
-      for (int r = 0; r < 2 * kMaxChunks; ++r) {
-        ctx->fold_wg_nrb[r] = 0;
-        for (int k = 0; k < 4; ++k) ctx->fold_wg_info[r][k] = 0.0;
-      }
-      ctx->fold_wg_read = true;
-      ctx->fold_path_last = fold.path;
-      ctx->fold_timed_last = false;
-      ctx->fold_cand_read = fold.path != 2;
-      ctx->n_cand_taken_last = ctx->n_cand_rerun_last = 0;
+    for (int c = 0; c < kMaxChunks; ++c) last.loss_listed_np[c] = 0;
+    last.loss_list_nt = nt;
+    last.loss_list_read = true;
+    last.n_loss_listed_launches = last.n_loss_live = last.n_loss_excl = 0;
+    for (int r = 0; r < 2 * kMaxChunks; ++r) {
+      last.fold_wg_nrb[r] = 0;
+      for (int k = 0; k < 4; ++k) last.fold_wg_info[r][k] = 0.0;
     }
+    last.fold_wg_read = true;
+    last.fold_path = res->fold_path = fold.path;
+    last.fold_timed = false;
+    last.fold_cand_read = fold.path != 2;
+    last.n_cand_taken = last.n_cand_rerun = 0;
     return SR_OK;
   }
 
@@ -947,13 +979,13 @@ struct BatchCall {
   // 2^17 rows has no such launch and keeps two chunks), every other call the two-chunk pipeline; and whether
   // the flags go back early (sr_ctx::exact_early).
   int plan_chunks() {
-    cplan = sr_chunk_plan(nt, ctx->chunks, ctx->first_chunk, ctx->chunk_min, multi, mode,
+    cplan = sr_chunk_plan(nt, ctx->chunks, ctx->first_chunk, ctx->chunk_min, multi, want.mode,
                           fold_compact && fold_cand && Rv == 16 ? ctx->tail_chunk : 0);  // (Rv 16: launch_region's cand_launch)
     n_chunks = cplan.n;
-    early = ctx->exact_early && ctx->want_early && fold.path != 0 && n_chunks > 1 && !multi && !shard && !parametric &&
-            mode == SR_MODE_LOSS;
+    early = ctx->exact_early && want.early && fold.path != 0 && n_chunks > 1 && !multi && !want.shard && !parametric &&
+            want.mode == SR_MODE_LOSS;
     if (early) SR_HIP_CHECK(ctx->need_stream3());
-    if (!ctx->internal_pass) ctx->early_last = early;
+    res->early = early;
     return SR_OK;
   }
 
@@ -967,16 +999,16 @@ struct BatchCall {
     ctx->outs_bytes_all = outs_bytes;
     SR_HIP_CHECK(ctx->outs.ensure(outs_bytes));
     // latency path (see host_io): results written to pinned host memory, programs read from it
-    const bool small_call = n_chunks == 1 && mode == SR_MODE_LOSS;
+    const bool small_call = n_chunks == 1 && want.mode == SR_MODE_LOSS;
     // (under the in-order fold the plan reads the call's flags and partials on the device; a stored-loss
     // fold of one row block of <= 256 rows — fold_tiny, the walk alone — reads and writes pinned memory)
     const bool fold_small = fold.path == 1 && n_rb == 1 && n_eval <= 256;
-    host_out = small_call && ctx->host_io >= 1 && ctx->want_host_out && (fold.path == 0 || fold_small);
+    host_out = small_call && ctx->host_io >= 1 && want.host_out && (fold.path == 0 || fold_small);
     // (other stored-loss folds of a small call: Σ and flags stay on the device for the pair kernel, and the
     //  walk copies them to pinned memory beside the fold's values — no copy back, SrFoldWho::msum)
-    fold_mirror = small_call && ctx->host_io >= 1 && ctx->want_host_out && fold.path == 1 && !fold_small && !shard;
+    fold_mirror = small_call && ctx->host_io >= 1 && want.host_out && fold.path == 1 && !fold_small && !want.shard;
     if (host_out || fold_mirror || early) SR_HIP_CHECK(ctx->h_outs.ensure(outs_bytes, s, ctx->stream2));
-    ctx->outs_on_host = host_out || fold_mirror;
+    res->outs_on_host = host_out || fold_mirror;
     host_red = host_out && ctx->host_reduce > 0 && !multi && n_rb > 1 && int64_t(n_part) <= ctx->host_reduce;
     ctx->host_reductions.clear();
     ctx->host_red_rb = n_rb;
@@ -984,13 +1016,13 @@ struct BatchCall {
     char* const sums_base = host_out ? ctx->h_outs.as<char>() : ctx->outs.as<char>();
     ctx->d_out_sum = reinterpret_cast<double*>(sums_base);
     ctx->d_out_flag = reinterpret_cast<uint32_t*>(sums_base + ctx->outs_flag_off);
-    if (mode == SR_MODE_PRED) SR_HIP_CHECK(ctx->pred.ensure(size_t(nt) * size_t(n_eval) * sizeof(T) + 16));
+    if (want.mode == SR_MODE_PRED) SR_HIP_CHECK(ctx->pred.ensure(size_t(nt) * size_t(n_eval) * sizeof(T) + 16));
     return SR_OK;
   }
 
   // Dead-tree hints (one word per launch position) and the probe's scratch partials.
   int prepare_hints() {
-    use_hint = ctx->dead_hints && mode == SR_MODE_LOSS && n_rb > 1;  // (hints are per position)
+    use_hint = ctx->dead_hints && want.mode == SR_MODE_LOSS && n_rb > 1;  // (hints are per position)
     if (use_hint) {
       // epoch-tagged hints: each call marks dead positions with its own epoch, so the array needs a
       // reset only when (re)allocated or when the epoch counter wraps
@@ -1044,13 +1076,13 @@ struct BatchCall {
   int begin_programs() {
     if (gather) {
       for (int64_t i = 0; i < n_rows_up; ++i)
-        if (row_idx[i] < 0 || row_idx[i] >= ds->n)
-          return set_error(SR_ERR_INVALID_ARG, "row index " + std::to_string(row_idx[i]) + " out of range");
+        if (req.row_idx[i] < 0 || req.row_idx[i] >= req.ds->n)
+          return set_error(SR_ERR_INVALID_ARG, "row index " + std::to_string(req.row_idx[i]) + " out of range");
       SR_HIP_CHECK(ctx->row_idx.ensure(size_t(n_rows_up) * sizeof(int64_t)));
     }
     if (multi)
       for (int64_t t = 0; t < nt; ++t)
-        if (views->tree_view[t] < 0 || views->tree_view[t] >= views->n_views)
+        if (req.views->tree_view[t] < 0 || req.views->tree_view[t] >= req.views->n_views)
           return set_error(SR_ERR_INVALID_ARG, "tree " + std::to_string(t) + ": view index out of range");
 
     prog->code.clear();
@@ -1070,13 +1102,14 @@ struct BatchCall {
     ctx->h_bad_last = h_bad;
     ctx->h_perm_last = h_perm;
     h_end = reinterpret_cast<uint32_t*>(hprog + img.o_end);
-    ctx->n_chunks_last = 0;
-    ctx->derived_last = false;
-    ctx->n_derived_last = 0;
-    ctx->timed_last = ctx->timing != 0;
-    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_start, s));
+    last.n_chunks = 0;
+    last.derived = false;
+    last.n_derived = 0;
+    last.timed = ctx->timing != 0 && !want.internal;  // (this run records its events)
+    if (last.timed) SR_HIP_CHECK(hipEventRecord(ctx->ev_start, s));
     if (gather)
-      SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, row_idx, size_t(n_rows_up) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+      SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, req.row_idx, size_t(n_rows_up) * sizeof(int64_t), hipMemcpyHostToDevice,
+                                  s));
     if (parametric && nt > 0 && p_stride > 0)  // (ahead of the chunks' join: both streams see the table)
       SR_HIP_CHECK(hipMemcpyAsync(ctx->ptab.p, ctx->h_ptab.p, size_t(nt) * size_t(p_stride) * sizeof(T), hipMemcpyHostToDevice, s));
     return SR_OK;
@@ -1089,32 +1122,35 @@ struct BatchCall {
     dld = (n_eval + kRowAlign - 1) / kRowAlign * kRowAlign;
     // (row-sharded calls pass `shard`: the choice then depends only on the trees and on statistics of
     // every shard, so all ranks compile the same programs and number their checked arrays alike)
-    max_abs_x = leaf_bound(shard ? shard->max_abs_x : ds->max_abs_x);
-    const int64_t derived_rows = shard ? shard->min_rows : n_eval;
+    max_abs_x = leaf_bound(want.shard ? want.shard->max_abs_x : req.ds->max_abs_x);
+    const int64_t derived_rows = want.shard ? want.shard->min_rows : n_eval;
     // (and only for calls with enough work: the column pass is one more launch, which a search's small
     // calls — tens of trees x 1e5 rows — would pay in latency for nothing)
-    if (allow_derived && ctx->derived && mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && derived_rows >= kDerivedMinRows &&
-        nt >= 64 && double(nt) * double(derived_rows) >= kDerivedMinWork && max_abs_x < double(tbig())) {  // (track_x off)
-      choose_derived(*trees, ctx->opsets[opset_id], ds->nf, &spec, &dmap);
+    if (allow_derived && ctx->derived && want.mode == SR_MODE_LOSS && tier == SR_TIER_BASIC &&
+        derived_rows >= kDerivedMinRows && nt >= 64 && double(nt) * double(derived_rows) >= kDerivedMinWork &&
+        max_abs_x < double(tbig())) {  // (track_x off)
+      choose_derived(*req.trees, ctx->opsets[req.opset_id], req.ds->nf, &spec, &dmap);
       if (spec.n > 0) {
         SR_HIP_CHECK(ctx->derived_cols.ensure(size_t(spec.n) * size_t(dld) * sizeof(T)));
-        if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_d0, s));
-        SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(ds->X), ds->ld, gather ? ctx->row_idx.as<int64_t>() : nullptr,
-                                          n_eval, dld, spec, ctx->derived_cols.as<T>(), dld, s));
-        if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_d1, s));
-        ctx->derived_last = true;
-        ctx->n_derived_last = spec.n;
+        if (last.timed) SR_HIP_CHECK(hipEventRecord(ctx->ev_d0, s));
+        SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(req.ds->X), req.ds->ld,
+                                          gather ? ctx->row_idx.as<int64_t>() : nullptr, n_eval, dld, spec,
+                                          ctx->derived_cols.as<T>(), dld, s));
+        if (last.timed) SR_HIP_CHECK(hipEventRecord(ctx->ev_d1, s));
+        last.derived = true;
+        last.n_derived = spec.n;
       } else {
         dmap.clear();
       }
     }
     // the probe over the dataset's stress rows (full views only: a gathered view's rows are its own);
     // its LOAD_DERIVED nodes read columns computed over those rows
-    stress_probe = use_probe && !gather && ds->probe_rows != nullptr && ctx->stress_probe;
+    stress_probe = use_probe && !gather && req.ds->probe_rows != nullptr && ctx->stress_probe;
     if (stress_probe && !dmap.empty()) {
       SR_HIP_CHECK(ctx->probe_derived.ensure(size_t(spec.n) * size_t(kProbeRows) * sizeof(T)));
-      SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(ds->X), ds->ld, static_cast<const int64_t*>(ds->probe_rows),
-                                        ds->n_probe, kProbeRows, spec, ctx->probe_derived.as<T>(), kProbeRows, s));
+      SR_HIP_CHECK(sr_launch_derived<T>(static_cast<const T*>(req.ds->X), req.ds->ld,
+                                        static_cast<const int64_t*>(req.ds->probe_rows), req.ds->n_probe, kProbeRows, spec,
+                                        ctx->probe_derived.as<T>(), kProbeRows, s));
     }
     return SR_OK;
   }
@@ -1136,7 +1172,7 @@ struct BatchCall {
     fjob.n_terms = fold_n_terms;
     fjob.delta = std::ldexp(1.0, -ctx->fold_delta_log2);
     // stored losses on one GPU: the pair kernel reduces the partials itself (one launch fewer a call)
-    fjob.fuse_reduce = fold.path == 1 && !shard && mode == SR_MODE_LOSS;
+    fjob.fuse_reduce = fold.path == 1 && !want.shard && want.mode == SR_MODE_LOSS;
     fjob.slot_cap = fold.path == 2
                         ? int(std::min<int64_t>({int64_t(INT_MAX / 2), fold.slot_budget,
                                                  int64_t(ctx->fold_store.cap / (size_t(fold.slot_rows) * sizeof(T)))}))
@@ -1154,17 +1190,17 @@ struct BatchCall {
     const int64_t t0 = ch.t0 = cplan.bound[ch.c];
     const int64_t nc = ch.nc = cplan.bound[ch.c + 1] - t0;
     for (int64_t t = t0; t < t0 + nc; ++t)
-      ch.max_nodes = std::max<uint32_t>(ch.max_nodes, uint32_t(trees->offsets[t + 1] - trees->offsets[t]));
+      ch.max_nodes = std::max<uint32_t>(ch.max_nodes, uint32_t(req.trees->offsets[t + 1] - req.trees->offsets[t]));
     // chunks alternate between two streams: chunk c+1's workgroups fill the GPU while chunk c drains
     ch.cs = (ch.c & 1) ? ctx->stream2 : s;
-    sr_tree_batch sub = *trees;
+    sr_tree_batch sub = *req.trees;
     sub.n_trees = nc;
-    sub.offsets = trees->offsets + t0;  // node arrays stay indexed by absolute offsets
+    sub.offsets = req.trees->offsets + t0;  // node arrays stay indexed by absolute offsets
     ch.pc.keep_pieces = true;  // (staged below straight from the compile workers' buffers)
     // (a parametric batch's per-node arrays are indexed by absolute node offsets, like the tree batch's)
     const SrParamNodes pnodes{parametric ? pb->is_parameter : nullptr, parametric ? pb->parameter : nullptr,
                               parametric ? pb->max_parameters : 0};
-    const int rc = sr_compile_batch<T>(sub, ctx->opsets[opset_id], n_total, ds->nf, false, &ch.pc, &err,
+    const int rc = sr_compile_batch<T>(sub, ctx->opsets[req.opset_id], want.n_total, req.ds->nf, false, &ch.pc, &err,
                                        dmap.empty() ? nullptr : dmap.data(), parametric ? &pnodes : nullptr);
     if (rc != SR_OK) {
       if (rc == SR_ERR_BAD_TREE || rc == SR_ERR_INVALID_ARG) {
@@ -1184,7 +1220,7 @@ struct BatchCall {
                      (long long)nt, n_chunks, std::chrono::duration<double, std::milli>(t_pre - ctx->phase_t).count(),
                      (long long)nc, std::chrono::duration<double, std::milli>(now - t_pre).count());
       }
-      ctx->mark_phase(0);
+      mark_phase(0);
     }
     ch.depth = ch.pc.max_depth > 0 ? ch.pc.max_depth : 1;
     ch.ncode = ch.pc.n_code;
@@ -1203,8 +1239,8 @@ struct BatchCall {
     if (code_base + ch.ncode > img.code_cap) return set_error(SR_ERR_INVALID_ARG, "program longer than its node count");
     std::memcpy(h_bad + t0, pc.static_bad.data(), size_t(nc));
     uint32_t* const perm = h_perm + t0;
-    sr_launch_order(pc.cost.data(), pc.depth.data(), nc, multi ? views->tree_view + t0 : nullptr,
-                    multi ? views->n_views : 0, ctx->cost_order, ctx->balance_groups, Rv > 0,
+    sr_launch_order(pc.cost.data(), pc.depth.data(), nc, multi ? req.views->tree_view + t0 : nullptr,
+                    multi ? req.views->n_views : 0, ctx->cost_order, ctx->balance_groups, Rv > 0,
                     GroupShape{ch.g_vs.G, ch.g_vs.n_groups}, GroupShape{ch.g_ls.G, ch.g_ls.n_groups}, perm);
     uint32_t* const off = h_off + t0;
     uint32_t* const end = h_end + t0;
@@ -1229,7 +1265,7 @@ struct BatchCall {
     }
     // (several views: Rv = 0, so the one launch's grid is g_ls)
     if (multi && nc > 0)
-      ch.seg_blocks = sr_view_segments(views->tree_view + t0, perm, nc, ch.g_ls.G, ch.g_ls.n_row_blocks, n_idx,
+      ch.seg_blocks = sr_view_segments(req.views->tree_view + t0, perm, nc, ch.g_ls.G, ch.g_ls.n_row_blocks, req.n_idx,
                                        reinterpret_cast<SrSegment*>(hprog + img.o_seg), &ch.n_seg);
     return SR_OK;
   }
@@ -1278,11 +1314,11 @@ struct BatchCall {
     a.hint_epoch = ctx->hint_epoch;
     a.n_trees = int(np);
     a.trees_per_block = g.G;
-    a.X = static_cast<const T*>(ds->X);
-    a.y = static_cast<const T*>(ds->y);
-    a.w = static_cast<const T*>(ds->w);
+    a.X = static_cast<const T*>(req.ds->X);
+    a.y = static_cast<const T*>(req.ds->y);
+    a.w = static_cast<const T*>(req.ds->w);
     a.row_idx = gather ? ctx->row_idx.as<int64_t>() : nullptr;
-    a.ld = ds->ld;
+    a.ld = req.ds->ld;
     a.derived = dmap.empty() ? nullptr : ctx->derived_cols.as<T>();
     a.dld = dld;
     a.n_rows = n_eval;
@@ -1299,12 +1335,12 @@ struct BatchCall {
     a.stack_depth = vstk ? std::min(ch.depth, SR_VSTK_SLOTS) : ch.depth;  // (the register-stack trees need <= SR_VSTK_SLOTS)
     a.tbig = tbig();
     {  // the view's padded rows over every shard: n_total + at most one 2048-row tile of padding per shard
-      const double padded = double(n_total > 0 ? n_total : 1) + 2048.0 * double(shard ? ctx->comm_ranks : 1);
+      const double padded = double(want.n_total > 0 ? want.n_total : 1) + 2048.0 * double(want.shard ? ctx->comm_ranks : 1);
       a.big_budget = 64.0 * (t_max<T>() / (1.01 * padded));  // (f64: 64 x DBL_MAX alone is +Inf)
     }
     a.track_x = !(max_abs_x < double(a.tbig)) ? 1 : 0;
 #ifdef SR_TRACK_LITE
-    if (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC) {
+    if (want.mode == SR_MODE_LOSS && tier == SR_TIER_BASIC) {
       // (the deferred-check kernels leave +, - of stack values / features and cos, sin, neg, abs,
       //  sqrt untracked: such a value is at most L x max(tracked max, max|x|, 1) for a tree of L
       //  nodes, so with tbig / L as the tracked threshold every value stays below tbig, and a tile
@@ -1340,7 +1376,7 @@ struct BatchCall {
     // (round 4's cache in the classic launches too — code_cache 2 — was measured without payoff and
     //  removed in round 6)
     const size_t code_budget = vstk ? kCodeCacheLds : 0;
-    if (mode == SR_MODE_LOSS && ctx->code_cache && size_t(g.lds) < code_budget) {
+    if (want.mode == SR_MODE_LOSS && ctx->code_cache && size_t(g.lds) < code_budget) {
       const int64_t maxspan = sr_max_group_span(h_perm + t0, h_off + t0, h_end + t0, p0, np, g.G, g.n_groups);
       const int64_t cap = int64_t((code_budget - size_t(g.lds)) / 16);
       a.code_lds = int(std::min(maxspan, cap));
@@ -1373,18 +1409,19 @@ struct BatchCall {
     pa.part_sum = ctx->probe_sum.as<double>();
     pa.part_flag = ctx->probe_flag.as<uint32_t>();
     if (stress_probe) {  // the stress rows first (sr_dataset::probe_rows), through the gather build
-      pa.row_idx = static_cast<const int64_t*>(ds->probe_rows);
-      pa.n_rows = std::min<int64_t>(ds->n_probe, int64_t(kProbeTiles) * 64 * R);
+      pa.row_idx = static_cast<const int64_t*>(req.ds->probe_rows);
+      pa.n_rows = std::min<int64_t>(req.ds->n_probe, int64_t(kProbeTiles) * 64 * R);
       if (!dmap.empty()) {
         pa.derived = ctx->probe_derived.as<T>();
         pa.dld = kProbeRows;
       }
     }
     if (parametric)
-      SR_HIP_CHECK(sr_launch_eval_param<T>(pa, pa_, mode, gather || stress_probe, tier, R, W, false,
+      SR_HIP_CHECK(sr_launch_eval_param<T>(pa, pa_, want.mode, gather || stress_probe, tier, R, W, false,
                                            pa.n_groups * kProbeTiles, ch.cs));
     else
-      SR_HIP_CHECK(sr_launch_eval<T>(pa, mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles, ch.cs));
+      SR_HIP_CHECK(sr_launch_eval<T>(pa, want.mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles,
+                                     ch.cs));
     return SR_OK;
   }
 
@@ -1396,7 +1433,7 @@ struct BatchCall {
     const int Rc = vstk ? Rv : R;
     const Grid& g = vstk ? ch.g_vs : ch.g_ls;
     if (g.lds > kLdsMax)
-      return set_error(SR_ERR_TOO_DEEP, "the row tile (" + std::to_string(ds->nf) + " features, " +
+      return set_error(SR_ERR_TOO_DEEP, "the row tile (" + std::to_string(req.ds->nf) + " features, " +
                                             std::to_string(ch.depth) + " stack slots) needs " + std::to_string(g.lds) +
                                             " bytes of LDS; the limit is 160 KiB");
     if (g.n_blocks > 0x7fffffff || g.n_row_blocks > n_rb) return set_error(SR_ERR_INVALID_ARG, "grid too large");
@@ -1411,7 +1448,7 @@ struct BatchCall {
       n_blocks = ch.seg_blocks;
       if (n_blocks > 0x7fffffff) return set_error(SR_ERR_INVALID_ARG, "grid too large");
     }
-    const bool direct = mode == SR_MODE_LOSS && g.n_row_blocks == 1;
+    const bool direct = want.mode == SR_MODE_LOSS && g.n_row_blocks == 1;
     if (direct) {  // the interpreter writes the final per-tree values; no reduce launch
       a.out_sum = ctx->d_out_sum + t0;
       a.out_flag = ctx->d_out_flag + t0;
@@ -1458,17 +1495,15 @@ struct BatchCall {
       // (a listed group's span takes in the excluded programs between its trees: the whole cache budget, and
       //  the kernel's own test per workgroup)
       if (a.code_lds > 0) a.code_lds = int((kCodeCacheLds - size_t(g.lds)) / 16);
-      if (!ctx->internal_pass) {
-        ctx->loss_listed_np[ch.c] = np;
-        ctx->loss_list_read = false;
-      }
+      last.loss_listed_np[ch.c] = np;
+      last.loss_list_read = false;
     }
     if (parametric)
-      SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
+      SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, want.mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
     else if (cand_launch)
       SR_HIP_CHECK(sr_launch_loss_cand<T>(a, Rc, g.W, int(n_blocks), cs));
     else
-      SR_HIP_CHECK(sr_launch_eval<T>(a, mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
+      SR_HIP_CHECK(sr_launch_eval<T>(a, want.mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
     if (fold.path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g, fold_compact ? sr_fold_region(ch.c, vstk) : -1});
     if (!direct && host_red)
       ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
@@ -1485,7 +1520,7 @@ struct BatchCall {
   // are final here (reduce / direct write ran on this stream)
   int fold_chunk(const BatchChunk<T>& ch) {
     hipStream_t cs = ch.cs;
-    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_fc0[ch.c], cs));
+    if (last.timed) SR_HIP_CHECK(hipEventRecord(ctx->ev_fc0[ch.c], cs));
     SrFoldWho who{ctx->d_out_sum, ctx->d_out_flag, fold_n_terms, nullptr, nullptr, 1};
     if (fold_mirror) {
       who.msum = ctx->h_outs.as<double>();
@@ -1496,9 +1531,9 @@ struct BatchCall {
       SR_STAGE(fold_walk<T>(ctx, fjob, fr, who, nullptr, d_fval, d_fst, cs));
     }
     fjob.regions.clear();
-    if (ctx->timed_last) {
+    if (last.timed) {
       SR_HIP_CHECK(hipEventRecord(ctx->ev_fc1[ch.c], cs));
-      ctx->fold_timed_last = true;
+      last.fold_timed = true;
     }
     return SR_OK;
   }
@@ -1510,10 +1545,10 @@ struct BatchCall {
     SR_STAGE(compile_chunk(ch));
     SR_STAGE(order_and_stage(ch));
     SR_STAGE(upload_chunk(ch));
-    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_c0[c], ch.cs));  // the chunk's kernel time includes its probe
+    if (last.timed) SR_HIP_CHECK(hipEventRecord(ctx->ev_c0[c], ch.cs));  // the chunk's kernel time includes its probe
     if (ch.n_vs > 0) SR_STAGE(launch_region(ch, 0, ch.n_vs, true));
     if (ch.n_vs < ch.nc) SR_STAGE(launch_region(ch, ch.n_vs, ch.nc - ch.n_vs, false));
-    if (ctx->timed_last) SR_HIP_CHECK(hipEventRecord(ctx->ev_c1[c], ch.cs));
+    if (last.timed) SR_HIP_CHECK(hipEventRecord(ctx->ev_c1[c], ch.cs));
     if (early) SR_HIP_CHECK(hipEventRecord(ctx->ev_red[c], ch.cs));
     if (early && c == n_chunks - 1) {  // every chunk's flags are final: to pinned memory, ahead of this chunk's chain
       for (int k = 0; k < c; ++k) SR_HIP_CHECK(hipStreamWaitEvent(ch.cs, ctx->ev_red[k], 0));
@@ -1521,14 +1556,14 @@ struct BatchCall {
                                   size_t(nt) * sizeof(uint32_t), hipMemcpyDeviceToHost, ch.cs));
       SR_HIP_CHECK(hipEventRecord(ctx->ev_flags, ch.cs));
     }
-    if (fold.path && !shard && !fjob.regions.empty()) SR_STAGE(fold_chunk(ch));
-    ctx->n_chunks_last = c + 1;
+    if (fold.path && !want.shard && !fjob.regions.empty()) SR_STAGE(fold_chunk(ch));
+    last.n_chunks = c + 1;
     code_base += uint32_t(ch.ncode);
     return SR_OK;
   }
 
   // The stages of a call, in order.
-  int run(Grid* grid_out) {
+  int run() {
     SR_STAGE(validate_call());
     SR_STAGE(stage_param_table());
     choose_kernels();
@@ -1546,20 +1581,18 @@ struct BatchCall {
       SR_HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->stream2));
       SR_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0));
     }
-    if (nt == 0) ctx->mark_phase(0);
-    *grid_out = glast;
-    if (fold.path && shard) ctx->fold_job = std::make_shared<FoldJob<T>>(std::move(fjob));  // (eval_sharded_impl)
-    ctx->mark_phase(1);
+    if (nt == 0) mark_phase(0);
+    res->grid = glast;
+    if (fold.path && want.shard) ctx->fold_job = std::make_shared<FoldJob<T>>(std::move(fjob));  // (eval_sharded_impl)
+    mark_phase(1);
     return SR_OK;
   }
 };
 
 template <typename T>
-int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, const int64_t* row_idx,
-              int64_t n_idx, int64_t n_total, int loss_kind, int mode, SrProgramBatch<T>* prog, Grid* grid_out,
-              bool allow_derived = false, const ShardCtl* shard = nullptr, const ViewSpec* views = nullptr) {
-  BatchCall<T> b{ctx, ds, opset_id, trees, row_idx, n_idx, n_total, loss_kind, mode, prog, allow_derived, shard, views};
-  const int rc = b.run(grid_out);
+int run_batch(sr_ctx* ctx, const EvalReq& req, const BatchWants& want, SrProgramBatch<T>* prog, BatchResult* res) {
+  BatchCall<T> b(ctx, req, want, prog, res);
+  const int rc = b.run();
   // error exits while work is in flight: no DMA may still read the staging buffers
   if (rc != SR_OK && b.in_flight) {
     (void)hipStreamSynchronize(ctx->stream);
@@ -1568,26 +1601,25 @@ int run_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_bat
   return rc;
 }
 // run_batch for the dataset's element type, for the callers that need only ctx->d_out_sum / d_out_flag
-inline int run_batch_any(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, int64_t n_total,
-                         int loss_kind, Grid* grid_out) {
-  if (ds->dtype == SR_DTYPE_F32) {
+inline int run_batch_any(sr_ctx* ctx, const EvalReq& req, const BatchWants& want, BatchResult* res) {
+  if (req.ds->dtype == SR_DTYPE_F32) {
     SrProgramBatch<float> prog;
-    return run_batch<float>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, grid_out);
+    return run_batch<float>(ctx, req, want, &prog, res);
   }
   SrProgramBatch<double> prog;
-  return run_batch<double>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, grid_out);
+  return run_batch<double>(ctx, req, want, &prog, res);
 }
 
-// Interpreter time of the last run_batch (ms): Σ of its launches' durations (as a kernel trace sums
-// them; chunks on the two streams may overlap, so this can exceed the wall time they span).
+// Interpreter time of the last call's own run_batch (sr_ctx::LastCall, ms): Σ of its launches' durations (as a
+// kernel trace sums them; chunks on the two streams may overlap, so this can exceed the wall time they span).
 inline double chunk_kernel_ms(sr_ctx* ctx) {
   double ms = 0.0;
-  if (!ctx->timed_last) return 0.0;
-  for (int c = 0; c < ctx->n_chunks_last; ++c) {
+  if (!ctx->last.timed) return 0.0;
+  for (int c = 0; c < ctx->last.n_chunks; ++c) {
     float m = 0.f;
     if (hipEventElapsedTime(&m, ctx->ev_c0[c], ctx->ev_c1[c]) == hipSuccess) ms += double(m);
   }
-  if (ctx->derived_last) {  // the derived columns are part of the call's interpreter work
+  if (ctx->last.derived) {  // the derived columns are part of the call's interpreter work
     float m = 0.f;
     if (hipEventElapsedTime(&m, ctx->ev_d0, ctx->ev_d1) == hipSuccess) ms += double(m);
   }
@@ -1598,16 +1630,16 @@ inline double chunk_kernel_ms(sr_ctx* ctx) {
 // streams overlap, so the sum above can exceed the wall time they span; this cannot).
 inline double chunk_busy_ms(sr_ctx* ctx) {
   std::vector<std::pair<double, double>> iv;
-  if (!ctx->timed_last) return 0.0;
+  if (!ctx->last.timed) return 0.0;
   auto add = [&](hipEvent_t a, hipEvent_t b) {
     float t0 = 0.f, t1 = 0.f;
     if (hipEventElapsedTime(&t0, ctx->ev_start, a) == hipSuccess && hipEventElapsedTime(&t1, ctx->ev_start, b) == hipSuccess)
       iv.push_back({double(t0), double(t1)});
   };
-  for (int c = 0; c < ctx->n_chunks_last; ++c) add(ctx->ev_c0[c], ctx->ev_c1[c]);
-  if (ctx->derived_last) add(ctx->ev_d0, ctx->ev_d1);
-  if (ctx->fold_timed_last)  // (the in-order fold's launches: device work of the call too)
-    for (int c = 0; c < ctx->n_chunks_last; ++c) add(ctx->ev_fc0[c], ctx->ev_fc1[c]);
+  for (int c = 0; c < ctx->last.n_chunks; ++c) add(ctx->ev_c0[c], ctx->ev_c1[c]);
+  if (ctx->last.derived) add(ctx->ev_d0, ctx->ev_d1);
+  if (ctx->last.fold_timed)  // (the in-order fold's launches: device work of the call too)
+    for (int c = 0; c < ctx->last.n_chunks; ++c) add(ctx->ev_fc0[c], ctx->ev_fc1[c]);
   std::sort(iv.begin(), iv.end());
   double busy = 0.0, lo = 0.0, hi = -1.0;
   for (const auto& [a, b] : iv) {
@@ -1779,14 +1811,14 @@ const JlLevels& jl_levels_cached(int64_t n) {
 // only enqueued — after a synchronisation of `st` the verdicts are at h_exact + *fin_off
 // ([n_list][max_checks]) and ev_k0 / ev_k1 bracket the pass.
 template <typename T>
-int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, const int64_t* row_idx,
-              int64_t n_idx, const int64_t* list, int64_t n_list, int max_checks, const std::vector<JlRange>& ranges,
-              T* host_vals, uint8_t* host_finite = nullptr, int64_t dev_row_off = 0, hipStream_t st = nullptr,
-              bool sync = true, size_t* fin_off = nullptr) {
+int run_exact(sr_ctx* ctx, const EvalReq& req, const SrProgramBatch<T>& prog, const int64_t* list, int64_t n_list,
+              int max_checks, const std::vector<JlRange>& ranges, T* host_vals, uint8_t* host_finite = nullptr,
+              int64_t dev_row_off = 0, hipStream_t st = nullptr, bool sync = true, size_t* fin_off = nullptr) {
   if (n_list == 0 || max_checks == 0 || ranges.empty()) return SR_OK;
   if (!sync && (!host_finite || !fin_off)) return set_error(SR_ERR_INVALID_ARG, "speculative exact pass: no verdict buffer");
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
+  const sr_dataset* const ds = req.ds;
+  const bool gather = req.gather();
+  const int64_t n_eval = req.n_eval();
   hipStream_t s = st ? st : ctx->stream;
   const int depth = prog.max_depth > 0 ? prog.max_depth : 1;
   const int R = sr_rows_per_lane<T>(SR_MODE_EXACT, SR_TIER_FULL, 0);
@@ -1797,9 +1829,9 @@ int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, 
     const char* v = std::getenv("SR_AMD_EXACT_TIER");
     return v && std::strcmp(v, "full") == 0;
   }();
-  // a parametric call (sr_ctx::param, the table of its run_batch still on the device): the PARAM builds
+  // a parametric call (EvalReq::params, the table of its run_batch still on the device): the PARAM builds
   // of the pass — the FULL-tier build, 4 waves — over the staged rows with the hidden class row
-  const sr_param_batch* const pb = ctx->param;
+  const sr_param_batch* const pb = req.params;
   const int nfk = int(ds->nf) + (pb ? 1 : 0);
   const int etier = (prog.tier == SR_TIER_BASIC && !exact_full && !pb) ? SR_TIER_BASIC : SR_TIER_FULL;
   const int64_t n_ranges = int64_t(ranges.size());
@@ -1944,22 +1976,18 @@ int run_exact(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, 
 // EXACT pass over the whole view on this GPU -> list_ok[i] = every checked array of tree list[i]
 // passes isfinite(Julia sum).
 template <typename T>
-int exact_list_ok(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, const int64_t* row_idx,
-                  int64_t n_idx, const std::vector<int64_t>& list, std::vector<uint8_t>* list_ok,
-                  int64_t dev_row_off = 0) {
+int exact_list_ok(sr_ctx* ctx, const EvalReq& req, const SrProgramBatch<T>& prog, const std::vector<int64_t>& list,
+                  std::vector<uint8_t>* list_ok, int64_t dev_row_off = 0) {
   list_ok->assign(list.size(), 1);
   if (list.empty() || prog.max_checks == 0) return SR_OK;
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
-  const std::vector<JlRange>& ranges = jl_ranges_cached(n_eval);
+  const std::vector<JlRange>& ranges = jl_ranges_cached(req.n_eval());
   // check slots: the most any LISTED tree has (the LDS image and the fold buffers scale with it)
   int mc = 0;
   for (int64_t t : list) mc = std::max(mc, int(prog.n_checks[size_t(t)]));
   if (mc == 0) return SR_OK;
   // leaf folds combined in recursion order on the device: only the verdicts come back
   std::vector<uint8_t> fin(list.size() * size_t(mc));
-  int rc = run_exact<T>(ctx, ds, prog, row_idx, n_idx, list.data(), int64_t(list.size()), mc, ranges, nullptr,
-                        fin.data(), dev_row_off);
+  int rc = run_exact<T>(ctx, req, prog, list.data(), int64_t(list.size()), mc, ranges, nullptr, fin.data(), dev_row_off);
   if (rc != SR_OK) return rc;
   for (size_t i = 0; i < list.size(); ++i)
     for (int k = 0; k < mc; ++k) (*list_ok)[i] &= fin[i * size_t(mc) + size_t(k)];
@@ -2048,16 +2076,14 @@ struct SubBatch {
 };
 
 // The parameter side of the same trees (a parametric call's fold passes): node arrays and matrices copied
-// alike; `swap` installs it as the context's running parametric batch until it goes out of scope.
+// alike (src NULL, a plain call: empty); the sub-request's `params` points at `b` (fold_prepare).
 template <typename T>
 struct SubParam {
   std::vector<uint8_t> isp;
   std::vector<uint16_t> par;
   std::vector<T> mats;
   sr_param_batch b{};
-  sr_ctx* ctx = nullptr;
-  const sr_param_batch* saved = nullptr;
-  SubParam(sr_ctx* c, const sr_tree_batch& trees, const int64_t* idx, size_t n) : ctx(c), saved(c->param) {
+  SubParam(const sr_param_batch* saved, const sr_tree_batch& trees, const int64_t* idx, size_t n) {
     if (!saved) return;
     const size_t stride = size_t(saved->max_parameters) * size_t(saved->n_classes);
     const T* src = static_cast<const T*>(saved->parameters);
@@ -2073,9 +2099,7 @@ struct SubParam {
       par.push_back(0);
     }
     b = sr_param_batch{isp.data(), par.data(), saved->max_parameters, saved->n_classes, mats.data()};
-    ctx->param = &b;
   }
-  ~SubParam() { ctx->param = saved; }
   SubParam(const SubParam&) = delete;
   SubParam& operator=(const SubParam&) = delete;
 };
@@ -2133,29 +2157,6 @@ struct FoldDev {
   }
 };
 
-// The fold's PRED passes are internal: the call's interpreter timing (its chunk events) and the kernel
-// it reports (rows per lane, derived columns) stay those of the call's own loss launches.
-struct KeepCallInfo {
-  sr_ctx* c;
-  int timing, n_chunks, n_derived, rows;
-  bool timed, derived;
-  explicit KeepCallInfo(sr_ctx* x)
-      : c(x), timing(x->timing), n_chunks(x->n_chunks_last), n_derived(x->n_derived_last), rows(x->rows_last),
-        timed(x->timed_last), derived(x->derived_last) {
-    x->timing = 0;
-    x->internal_pass = true;
-  }
-  ~KeepCallInfo() {
-    c->internal_pass = false;
-    c->timing = timing;
-    c->n_chunks_last = n_chunks;
-    c->n_derived_last = n_derived;
-    c->rows_last = rows;
-    c->timed_last = timed;
-    c->derived_last = derived;
-  }
-};
-
 // Trees per PRED pass of the fold: predictions of at most `budget` bytes (and half the free device
 // memory when `use_free`; the row-sharded call uses a fixed budget so that every rank cuts the list
 // alike).
@@ -2165,23 +2166,31 @@ inline int64_t fold_batch_trees(int64_t n_eval, size_t elem, bool use_free) {
   return std::max<int64_t>(1, int64_t(budget / (size_t(std::max<int64_t>(n_eval, 1)) * elem)));
 }
 
-// One batch of listed trees, first half: the PRED interpreter over this view (or shard) into ctx->pred,
-// the device scratch bound, and (segmented) the segment sums.
+// One batch of listed trees, first half: the PRED interpreter over this view (or shard) into ctx->pred —
+// an internal pass (BatchWants::internal) over a sub-request: these trees, and in a parametric call their
+// own parameter side — the device scratch bound, and (segmented) the segment sums.
 template <typename T>
-int fold_prepare(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, const int64_t* row_idx,
-                 int64_t n_idx, int64_t n_total, int loss_kind, const int64_t* list, size_t nb, int64_t seg_len,
+int fold_prepare(sr_ctx* ctx, const EvalReq& req, int64_t n_total, const int64_t* list, size_t nb, int64_t seg_len,
                  FoldDev<T>* fd) {
   int lkind = 0;
   double lparam = 0.0;
-  if (decode_loss(ctx, loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
-  SubBatch<T> sub(*trees, list, nb);
-  SubParam<T> subp(ctx, *trees, list, nb);  // (a parametric call: these trees' parameter side, for this pass)
+  if (decode_loss(ctx, req.loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
+  const sr_dataset* const ds = req.ds;
+  const int64_t n_eval = req.n_eval();
+  SubBatch<T> sub(*req.trees, list, nb);
+  SubParam<T> subp(req.params, *req.trees, list, nb);
+  EvalReq sreq = req;
+  sreq.trees = &sub.b;
+  sreq.params = req.params ? &subp.b : nullptr;
+  sreq.views = nullptr;
+  BatchWants want;
+  want.mode = SR_MODE_PRED;
+  want.n_total = n_total;
+  want.internal = true;
   SrProgramBatch<T> prog;
-  Grid g;
+  BatchResult res;
   SR_HIP_CHECK(hipEventRecord(ctx->ev_f[0], ctx->stream));
-  int rc = run_batch<T>(ctx, ds, opset_id, &sub.b, row_idx, n_idx, n_total, loss_kind, SR_MODE_PRED, &prog, &g);
+  int rc = run_batch<T>(ctx, sreq, want, &prog, &res);
   if (rc != SR_OK) return rc;
   SR_HIP_CHECK(hipEventRecord(ctx->ev_f[1], ctx->stream));
   const int64_t n_seg = seg_len > 0 ? (n_eval + seg_len - 1) / seg_len : 0;
@@ -2189,7 +2198,7 @@ int fold_prepare(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_
   fd->bind(ctx->fold_io.p, nb, n_seg);
   if (seg_len > 0)
     SR_HIP_CHECK(sr_launch_fold_segsum<T>(ctx->pred.as<T>(), n_eval, int(nb), static_cast<const T*>(ds->y),
-                                          static_cast<const T*>(ds->w), gather ? ctx->row_idx.as<int64_t>() : nullptr,
+                                          static_cast<const T*>(ds->w), req.gather() ? ctx->row_idx.as<int64_t>() : nullptr,
                                           n_eval, lkind, T(lparam), seg_len, fd->segsum, ctx->stream));
   SR_HIP_CHECK(hipEventRecord(ctx->ev_f[2], ctx->stream));
   return SR_OK;
@@ -2198,17 +2207,16 @@ int fold_prepare(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_
 // Second half: the segments' composed steps (carry_est: device, per tree, or NULL) and the chain
 // (carry: device, per tree, or NULL); the folds into out (host) after one synchronisation.
 template <typename T>
-int fold_finish(sr_ctx* ctx, const sr_dataset* ds, const int64_t* row_idx, int64_t n_idx, int loss_kind, size_t nb,
-                int64_t seg_len, const FoldDev<T>& fd, bool with_carry_est, bool with_carry, T* out) {
+int fold_finish(sr_ctx* ctx, const EvalReq& req, size_t nb, int64_t seg_len, const FoldDev<T>& fd, bool with_carry_est,
+                bool with_carry, T* out) {
   int lkind = 0;
   double lparam = 0.0;
-  if (decode_loss(ctx, loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
+  if (decode_loss(ctx, req.loss_kind, &lkind, &lparam) != SR_OK) return SR_ERR_INVALID_ARG;
+  const int64_t n_eval = req.n_eval();
   hipStream_t s = ctx->stream;
-  const T* y = static_cast<const T*>(ds->y);
-  const T* w = static_cast<const T*>(ds->w);
-  const int64_t* ri = gather ? ctx->row_idx.as<int64_t>() : nullptr;
+  const T* y = static_cast<const T*>(req.ds->y);
+  const T* w = static_cast<const T*>(req.ds->w);
+  const int64_t* ri = req.gather() ? ctx->row_idx.as<int64_t>() : nullptr;
   if (seg_len > 0)
     SR_HIP_CHECK(sr_launch_fold_segtab<T>(ctx->pred.as<T>(), n_eval, int(nb), y, w, ri, n_eval, lkind, T(lparam),
                                           seg_len, fd.segsum, with_carry_est ? fd.carry_est : nullptr, fd.tq, fd.tab, s));
@@ -2234,22 +2242,18 @@ int fold_finish(sr_ctx* ctx, const sr_dataset* ds, const int64_t* row_idx, int64
 // saw), then the segmented fold.  out: the folds (T; +Inf where the fold overflows).  Runs after the
 // call's other passes (it reuses the context's program buffers).
 template <typename T>
-int fold_exact(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, const int64_t* row_idx,
-               int64_t n_idx, int64_t n_total, int loss_kind, const std::vector<int64_t>& list, std::vector<T>* out) {
+int fold_exact(sr_ctx* ctx, const EvalReq& req, int64_t n_total, const std::vector<int64_t>& list, std::vector<T>* out) {
   out->assign(list.size(), T(0));
   if (list.empty()) return SR_OK;
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
+  const int64_t n_eval = req.n_eval();
   const int64_t seg_len = fold_seg_len(ctx, n_eval);
-  KeepCallInfo keep(ctx);
   const int64_t per = fold_batch_trees(n_eval, sizeof(T), true);
   for (size_t b0 = 0; b0 < list.size(); b0 += size_t(per)) {
     const size_t nb = std::min(list.size() - b0, size_t(per));
     FoldDev<T> fd;
-    int rc = fold_prepare<T>(ctx, ds, opset_id, trees, row_idx, n_idx, n_total, loss_kind, list.data() + b0, nb, seg_len,
-                             &fd);
+    int rc = fold_prepare<T>(ctx, req, n_total, list.data() + b0, nb, seg_len, &fd);
     if (rc != SR_OK) return rc;
-    rc = fold_finish<T>(ctx, ds, row_idx, n_idx, loss_kind, nb, seg_len, fd, false, false, out->data() + b0);
+    rc = fold_finish<T>(ctx, req, nb, seg_len, fd, false, false, out->data() + b0);
     if (rc != SR_OK) return rc;
   }
   release_large_pred(ctx);
@@ -2345,24 +2349,19 @@ double view_denominator(const sr_dataset* ds, const int64_t* row_idx, int64_t n_
   return s;
 }
 
-
-// views (may be NULL): several row views in one call (sr_eval_loss_batch_views); row_idx then holds
-// views->n_views views of n_idx rows each.
-// The second half of an eval_loss call: what finishing it needs once its device work is enqueued.
+// The second half of an eval_loss call: what finishing it needs once its device work is enqueued — the
+// request (with copies of the tree batch's and the views' structs, which it then points at) and what
+// run_batch handed back.
 template <typename T>
 struct LossCall {
-  const sr_dataset* ds = nullptr;
-  int opset_id = 0, loss_kind = 0;
+  EvalReq req;
   sr_tree_batch trees{};
-  const int64_t* row_idx = nullptr;
-  int64_t n_idx = 0;
+  ViewSpec views{};
   void* out_loss = nullptr;
   uint8_t* out_complete = nullptr;
-  bool has_views = false;
-  ViewSpec views{};
   SrProgramBatch<T> prog;
   std::chrono::steady_clock::time_point t0;
-  bool early = false;  // run_batch copied the flags early (sr_ctx::exact_early): finish copies the results back
+  BatchResult res;  // (early: finish copies the results back; fold_path: the walk's folds are among them)
 };
 template <typename T>
 int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c);
@@ -2370,45 +2369,33 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c);
 // First half: compile, stage, launch, and the copy of {Σ, flags} (or the kernel's own writes into
 // pinned memory); *c holds what eval_loss_finish needs.
 template <typename T>
-int eval_loss_submit(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                     const int64_t* row_idx, int64_t n_idx, int loss_kind, void* out_loss, uint8_t* out_complete,
-                     const ViewSpec* views, LossCall<T>* c) {
-  const int64_t nt = trees->n_trees;
+int eval_loss_submit(sr_ctx* ctx, const EvalReq& req, void* out_loss, uint8_t* out_complete, LossCall<T>* c) {
+  const int64_t nt = req.trees->n_trees;
   if (nt > 0 && (!out_loss || !out_complete)) return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
-  auto t0 = std::chrono::steady_clock::now();
-  ctx->start_phases(t0);
-  c->ds = ds;
-  c->opset_id = opset_id;
-  c->loss_kind = loss_kind;
-  c->trees = *trees;
-  c->row_idx = row_idx;
-  c->n_idx = n_idx;
+  c->t0 = std::chrono::steady_clock::now();
+  ctx->start_phases(c->t0);
+  c->req = req;
+  c->trees = *req.trees;
+  c->req.trees = &c->trees;
+  if (req.views) {
+    c->views = *req.views;
+    c->req.views = &c->views;
+  }
   c->out_loss = out_loss;
   c->out_complete = out_complete;
-  c->has_views = views != nullptr;
-  if (views) c->views = *views;
-  c->t0 = t0;
-  SrProgramBatch<T>& prog = c->prog;
-  Grid g;
-  ctx->want_host_out = true;
-  ctx->want_fold = true;
-  ctx->want_early = true;
-  ctx->early_last = false;
-  int rc = run_batch<T>(ctx, ds, opset_id, trees, row_idx, n_idx, n_eval, loss_kind, SR_MODE_LOSS, &prog, &g, true,
-                        nullptr, views);
-  ctx->want_host_out = false;
-  ctx->want_fold = false;
-  ctx->want_early = false;
+  BatchWants want;
+  want.n_total = req.n_eval();
+  want.allow_derived = true;
+  want.host_out = want.fold = want.early = true;
+  want.takes_expr = req.params == nullptr;  // (plain trees only: kLossExprOnly)
+  const int rc = run_batch<T>(ctx, req, want, &c->prog, &c->res);
   if (rc != SR_OK) return rc;
   if (nt == 0) return SR_OK;
   hipStream_t s = ctx->stream;
-  c->early = ctx->early_last;
-  if (c->early) return SR_OK;  // (eval_loss_finish: the exact-sum pass first, then the one copy back)
+  if (c->res.early) return SR_OK;  // (eval_loss_finish: the exact-sum pass first, then the one copy back)
   // {Σ loss, flags} of every tree: already in pinned memory (host_io), or one DMA there
-  if (!ctx->outs_on_host) {
-    const size_t out_bytes = ctx->fold_path_last ? ctx->outs_bytes_all : ctx->outs_flag_off + size_t(nt) * sizeof(uint32_t);
+  if (!c->res.outs_on_host) {
+    const size_t out_bytes = c->res.fold_path ? ctx->outs_bytes_all : ctx->outs_flag_off + size_t(nt) * sizeof(uint32_t);
     SR_HIP_CHECK(ctx->h_outs.ensure(out_bytes, s, ctx->stream2));
     SR_HIP_CHECK(hipMemcpyAsync(ctx->h_outs.p, ctx->outs.p, out_bytes, hipMemcpyDeviceToHost, s));
   }
@@ -2417,24 +2404,16 @@ int eval_loss_submit(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_t
 
 template <typename T>
 int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
-  const sr_dataset* ds = c.ds;
-  const int opset_id = c.opset_id;
-  const sr_tree_batch* trees = &c.trees;
-  const int64_t* row_idx = c.row_idx;
-  const int64_t n_idx = c.n_idx;
-  const int loss_kind = c.loss_kind;
-  void* out_loss = c.out_loss;
-  uint8_t* out_complete = c.out_complete;
-  const ViewSpec* views = c.has_views ? &c.views : nullptr;
+  const EvalReq& q = c.req;
+  const sr_dataset* const ds = q.ds;
+  const ViewSpec* const views = q.views;
   SrProgramBatch<T>& prog = c.prog;
-  const auto t0 = c.t0;
-  const int64_t nt = trees->n_trees;
+  const int64_t nt = q.trees->n_trees;
   if (nt == 0) return SR_OK;
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
+  const int64_t n_eval = q.n_eval();
   const int n_views = views ? views->n_views : 1;
   auto view_of = [&](int64_t t) -> int { return views ? int(views->tree_view[t]) : 0; };
-  auto rows_of = [&](int v) -> const int64_t* { return gather ? row_idx + int64_t(v) * n_idx : nullptr; };
+  auto rows_of = [&](int v) -> const int64_t* { return q.view(v).row_idx; };
   hipStream_t s = ctx->stream;
   int rc = SR_OK;
 
@@ -2447,7 +2426,7 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
   std::vector<int64_t> list;
   std::vector<uint8_t> list_ok;
   bool exact_done = false;
-  if (c.early) {
+  if (c.res.early) {
     // (sr_ctx::exact_early) the flags are in pinned memory once ev_flags has fired — the last chunk's chain
     // still runs; the BIG trees' exact-sum pass is enqueued beside it, then the results' copy behind every
     // stream, and one synchronisation covers both
@@ -2468,8 +2447,8 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
       size_t fin_off = 0;
       hipStream_t xs = ctx->stream3;  // (no chain occupies it)
       if (one_batch) {
-        SR_STAGE(run_exact<T>(ctx, ds, prog, row_idx, n_idx, list.data(), int64_t(list.size()), mc, ranges, nullptr,
-                              fin.data(), 0, xs, false, &fin_off));
+        SR_STAGE(run_exact<T>(ctx, q, prog, list.data(), int64_t(list.size()), mc, ranges, nullptr, fin.data(), 0, xs,
+                              false, &fin_off));
         SR_HIP_CHECK(hipEventRecord(ctx->ev_join, xs));
         SR_HIP_CHECK(hipStreamWaitEvent(s, ctx->ev_join, 0));
       }
@@ -2498,7 +2477,7 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
   std::vector<double> sums(hs, hs + nt);
   std::vector<uint32_t> flags(hf, hf + nt);
   ctx->timing_pending = true;
-  if (!c.early) {
+  if (!c.res.early) {
     ctx->mark_phase(2);
     big_list(flags.data(), &list);
     list_ok.assign(list.size(), 1);
@@ -2515,13 +2494,13 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
       }
     if (lv.empty()) continue;
     std::vector<uint8_t> ok;
-    rc = exact_list_ok<T>(ctx, ds, prog, rows_of(v), n_idx, lv, &ok, int64_t(v) * n_idx);
+    rc = exact_list_ok<T>(ctx, q.view(v), prog, lv, &ok, int64_t(v) * q.n_idx);
     if (rc != SR_OK) return rc;
     for (size_t i = 0; i < lv.size(); ++i) list_ok[at[i]] = ok[i];
   }
   ctx->mark_phase(3);
   std::vector<double> vden(static_cast<size_t>(n_views)), denoms;
-  for (int v = 0; v < n_views; ++v) vden[size_t(v)] = view_denominator<T>(ds, rows_of(v), n_idx);
+  for (int v = 0; v < n_views; ++v) vden[size_t(v)] = view_denominator<T>(ds, rows_of(v), q.n_idx);
   if (views) {
     denoms.resize(size_t(nt));
     for (int64_t t = 0; t < nt; ++t) denoms[size_t(t)] = vden[size_t(view_of(t))];
@@ -2530,7 +2509,7 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
   // the in-order fold's results (sr_ctx::ref_fold) and the reference's T denominators per view
   std::vector<T> tden(static_cast<size_t>(n_views));
   FoldResults<T> fres;
-  const bool have_fold = ctx->fold_path_last != 0;
+  const bool have_fold = c.res.fold_path != 0;
   if (have_fold) {
     for (int v = 0; v < n_views; ++v)
       tden[size_t(v)] = (ds->w && n_eval > 0) ? jl_wsum_view<T>(ds, rows_of(v), n_eval) : T(double(n_eval));
@@ -2540,7 +2519,7 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
     fres.debug_fail = ctx->fold_debug_fail;
   }
   finalize<T>(nt, sums.data(), flags.data(), vden[0], list.data(), int64_t(list.size()), list_ok.data(),
-              static_cast<T*>(out_loss), out_complete, fold_terms(ds, n_eval, loss_kind), &fold_list,
+              static_cast<T*>(c.out_loss), c.out_complete, fold_terms(ds, n_eval, q.loss_kind), &fold_list,
               views ? denoms.data() : nullptr, have_fold ? &fres : nullptr);
   ctx->n_ref_ok_last = fres.n_ok;
   ctx->n_ref_fail_last = fres.n_fail;
@@ -2567,7 +2546,7 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
         }
       }
       std::fprintf(stderr, "[sr fold] path %d: %lld walks, mean/max slow segments %.1f/%d, rounds %.1f/%d, slow-segment us %.1f/%d, walk us %.1f/%d; folded %lld fallback %lld\n",
-                   ctx->fold_path_last, (long long)m, m ? a[0] / m : 0.0, mx[0], m ? a[1] / m : 0.0, mx[1],
+                   c.res.fold_path, (long long)m, m ? a[0] / m : 0.0, mx[0], m ? a[1] / m : 0.0, mx[1],
                    m ? a[2] / m : 0.0, mx[2], m ? a[3] / m : 0.0, mx[3], (long long)fres.n_ok, (long long)fres.n_fail);
       std::fprintf(stderr, "[sr fold] slow segments advanced by their steps (no rows read): %lld\n", (long long)n_skip);
     }
@@ -2581,41 +2560,38 @@ int eval_loss_finish(sr_ctx* ctx, LossCall<T>& c) {
       if (view_of(t) == v) fv.push_back(t);
     if (fv.empty()) continue;
     std::vector<T> fold;
-    rc = fold_exact<T>(ctx, ds, opset_id, trees, rows_of(v), n_idx, n_eval, loss_kind, fv, &fold);
+    rc = fold_exact<T>(ctx, q.view(v), n_eval, fv, &fold);
     if (rc != SR_OK) return rc;
     // mean: total / count, in T; weighted: total / sum(w), the reference's pairwise Base.sum in T
     const T den = (ds->w && n_eval > 0) ? jl_wsum_view<T>(ds, rows_of(v), n_eval) : T(vden[size_t(v)]);
-    for (size_t i = 0; i < fv.size(); ++i) static_cast<T*>(out_loss)[fv[i]] = T(fold[i] / den);
+    for (size_t i = 0; i < fv.size(); ++i) static_cast<T*>(c.out_loss)[fv[i]] = T(fold[i] / den);
   }
   ctx->mark_phase(4);
   auto t1 = std::chrono::steady_clock::now();
-  ctx->last_total_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  (void)n_eval;
+  ctx->last_total_ms = std::chrono::duration<double, std::milli>(t1 - c.t0).count();
   return SR_OK;
 }
 
 // The whole call (sr_eval_loss_batch / _views): submit, then finish.
 template <typename T>
-int eval_loss_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                   const int64_t* row_idx, int64_t n_idx, int loss_kind, void* out_loss, uint8_t* out_complete,
-                   const ViewSpec* views = nullptr) {
+int eval_loss_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, uint8_t* out_complete) {
   LossCall<T> c;
-  const int rc = eval_loss_submit<T>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete, views,
-                                     &c);
+  const int rc = eval_loss_submit<T>(ctx, req, out_loss, out_complete, &c);
   if (rc != SR_OK) return rc;
   return eval_loss_finish<T>(ctx, c);
 }
 
 template <typename T>
-int eval_pred_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                   const int64_t* row_idx, int64_t n_idx, void* out_pred, uint8_t* out_complete) {
-  const int64_t nt = trees->n_trees;
+int eval_pred_impl(sr_ctx* ctx, const EvalReq& req, void* out_pred, uint8_t* out_complete) {
+  const int64_t nt = req.trees->n_trees;
   if (nt > 0 && (!out_pred || !out_complete)) return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
+  const int64_t n_eval = req.n_eval();
   SrProgramBatch<T> prog;
-  Grid g;
-  int rc = run_batch<T>(ctx, ds, opset_id, trees, row_idx, n_idx, n_eval, SR_LOSS_L2DIST, SR_MODE_PRED, &prog, &g);
+  BatchWants want;
+  want.mode = SR_MODE_PRED;
+  want.n_total = n_eval;
+  BatchResult res;
+  int rc = run_batch<T>(ctx, req, want, &prog, &res);
   if (rc != SR_OK) return rc;
   if (nt == 0) return SR_OK;
   hipStream_t s = ctx->stream;
@@ -2628,7 +2604,7 @@ int eval_pred_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
   for (int64_t t = 0; t < nt; ++t)
     if ((flags[t] & (SR_FLAG_NONFINITE | SR_FLAG_STATIC)) == 0 && (flags[t] & SR_FLAG_BIG)) list.push_back(t);
   std::vector<uint8_t> list_ok;
-  rc = exact_list_ok<T>(ctx, ds, prog, row_idx, n_idx, list, &list_ok);
+  rc = exact_list_ok<T>(ctx, req, prog, list, &list_ok);
   if (rc != SR_OK) return rc;
   std::vector<T> dummy(static_cast<size_t>(nt));
   finalize<T>(nt, sums.data(), flags.data(), 1.0, list.data(), int64_t(list.size()), list_ok.data(), dummy.data(),
@@ -2760,36 +2736,35 @@ int upload_impl(sr_ctx* ctx, const void* X, int64_t nf, int64_t n, const void* y
 
 // Batched forward-mode gradient (sr_eval_grad_batch): exact loss + complete flags from the loss
 // kernel, then d loss / d constants of every complete tree from the tangent kernel.
-// views (may be NULL): several row views in one call (sr_eval_grad_batch_views), as eval_loss_impl.
 template <typename T>
-int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                   const int64_t* row_idx, int64_t n_idx, int loss_kind, void* out_loss, void* out_grad,
-                   uint8_t* out_complete, const ViewSpec* views = nullptr) {
-  const SrOpset& ops = ctx->opsets[opset_id];
+int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_grad, uint8_t* out_complete) {
+  const sr_dataset* const ds = req.ds;
+  const sr_tree_batch* const trees = req.trees;
+  const SrOpset& ops = ctx->opsets[req.opset_id];
   for (uint32_t u : ops.unary)
     if (!sr_unary_grad_supported(u)) return set_error(SR_ERR_UNSUPPORTED_OP, "operator without a gradient rule");
   for (uint32_t b : ops.binary)
     if (!sr_binary_grad_supported(b)) return set_error(SR_ERR_UNSUPPORTED_OP, "operator without a gradient rule");
+  // a parametric call (EvalReq::params; the entry point has checked the batch against the dataset): the
+  // tree's tangents are its constants, then the parameters it uses (a compact rank: an unused parameter
+  // makes no tangent, no window and no work item), and the gradient of tree t is [its nc constants | K x C
+  // parameter entries, column-major] (sr_param_pack.h)
+  const sr_param_batch* const pb = req.params;
+  const bool parametric = pb != nullptr;
   int lkind = 0;
   double lparam = 0.0;
   const sr_ctx::LossExpr* lexpr = nullptr;  // (plain trees only: the loss pass below refuses a parametric call's)
-  if (decode_loss(ctx, loss_kind, &lkind, &lparam, ctx->param == nullptr ? &lexpr : nullptr) != SR_OK) return SR_ERR_INVALID_ARG;
+  if (decode_loss(ctx, req.loss_kind, &lkind, &lparam, parametric ? nullptr : &lexpr) != SR_OK) return SR_ERR_INVALID_ARG;
   if (lexpr && !lexpr->p32.grad_ok)
     return set_error(SR_ERR_UNSUPPORTED_OP, "the loss expression uses an operator without a gradient rule");
-  int rc = eval_loss_impl<T>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete, views);
+  int rc = eval_loss_impl<T>(ctx, req, out_loss, out_complete);
   if (rc != SR_OK) return rc;
   const int64_t nt = trees->n_trees;
   if (nt == 0) return SR_OK;
-  const bool gather = row_idx != nullptr && n_idx > 0;
-  const int64_t n_eval = gather ? n_idx : ds->n;
-  const int n_views = (views && gather) ? views->n_views : 1;
-  auto view_of = [&](int64_t t) -> int { return n_views > 1 ? int(views->tree_view[t]) : 0; };
-  // a parametric call (sr_ctx::param, set by the *_parametric entry points; the loss pass above has
-  // checked the batch against the dataset): the tree's tangents are its constants, then the parameters it
-  // uses (a compact rank: an unused parameter makes no tangent, no window and no work item), and the
-  // gradient of tree t is [its nc constants | K x C parameter entries, column-major] (sr_param_pack.h)
-  const sr_param_batch* const pb = ctx->param;
-  const bool parametric = pb != nullptr;
+  const bool gather = req.gather();
+  const int64_t n_eval = req.n_eval();
+  const int n_views = (req.views && gather) ? req.views->n_views : 1;
+  auto view_of = [&](int64_t t) -> int { return n_views > 1 ? int(req.views->tree_view[t]) : 0; };
   const int64_t pK = parametric ? pb->max_parameters : 0, pC = parametric ? pb->n_classes : 0;
   const SrParamNodes pnodes{parametric ? pb->is_parameter : nullptr, parametric ? pb->parameter : nullptr,
                             int32_t(pK)};
@@ -2867,8 +2842,8 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
   hipStream_t s = ctx->stream;
   // the loss pass's in-order folds re-upload their own view's rows: put every view's rows back
   if (gather && ctx->n_fold_last > 0) {
-    SR_HIP_CHECK(ctx->row_idx.ensure(size_t(n_views) * size_t(n_idx) * sizeof(int64_t)));
-    SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, row_idx, size_t(n_views) * size_t(n_idx) * sizeof(int64_t),
+    SR_HIP_CHECK(ctx->row_idx.ensure(size_t(n_views) * size_t(req.n_idx) * sizeof(int64_t)));
+    SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, req.row_idx, size_t(n_views) * size_t(req.n_idx) * sizeof(int64_t),
                                 hipMemcpyHostToDevice, s));
   }
   // several views: each bucket's work items ordered by view (stable), one segment per view; the
@@ -2895,7 +2870,7 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
         sg.pos0 = int(p);
         sg.n_pos = int(q - p);
         sg.groups = int((q - p + kWaves - 1) / kWaves);
-        sg.row_off = int64_t(v) * n_idx;
+        sg.row_off = int64_t(v) * req.n_idx;
         segs[b].push_back(sg);
         p = q;
       }
@@ -2970,7 +2945,7 @@ int eval_grad_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tre
   char* ds_ = ctx->g_code.as<char>();
   SR_HIP_CHECK(ctx->g_out.ensure(n_vals_all * sizeof(double) + 16));
   std::vector<double> vden(static_cast<size_t>(n_views));
-  for (int v = 0; v < n_views; ++v) vden[size_t(v)] = view_denominator<T>(ds, gather ? row_idx + int64_t(v) * n_idx : nullptr, n_idx);
+  for (int v = 0; v < n_views; ++v) vden[size_t(v)] = view_denominator<T>(ds, req.view(v).row_idx, req.n_idx);
   size_t part_need = 0;
   struct Launch { int64_t n_rb, tiles_per_block, n_groups; int rows, depth; };
   Launch lc[kNB] = {};
@@ -3379,8 +3354,9 @@ int shard_layout(sr_ctx* ctx, const sr_dataset* ds) {
 // every rank adds them in Base.mapreduce_impl's recursion order.  Collective (the list is the same on
 // every rank: it comes from the all-reduced flags); a local failure travels in the error word.
 template <typename T>
-int exact_sharded(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& prog, const std::vector<int64_t>& list,
+int exact_sharded(sr_ctx* ctx, const EvalReq& req, const SrProgramBatch<T>& prog, const std::vector<int64_t>& list,
                   std::vector<uint8_t>* list_ok) {
+  const sr_dataset* const ds = req.ds;
   list_ok->assign(list.size(), 1);
   int mc = 0;
   for (int64_t t : list) mc = std::max(mc, int(prog.n_checks[size_t(t)]));
@@ -3388,7 +3364,7 @@ int exact_sharded(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& pr
   const int nr = ctx->comm_ranks, me = ctx->comm_rank;
   const std::vector<int64_t>& offs = ds->shard_offs;
   const int64_t n_total = offs[size_t(nr)];
-  if (nr == 1) return exact_list_ok<T>(ctx, ds, prog, nullptr, 0, list, list_ok);  // one shard = the whole view
+  if (nr == 1) return exact_list_ok<T>(ctx, req, prog, list, list_ok);  // one shard = the whole view
   std::vector<std::vector<JlRange>> ranges(static_cast<size_t>(nr));
   size_t max_r = 0;
   for (int r = 0; r < nr; ++r) {
@@ -3400,7 +3376,7 @@ int exact_sharded(sr_ctx* ctx, const sr_dataset* ds, const SrProgramBatch<T>& pr
   const size_t payload = n_arrays * max_r * sizeof(T);
   const size_t slot = (payload + sizeof(double) + 255) & ~size_t(255);
   std::vector<char> mine(slot, 0);
-  int local = run_exact<T>(ctx, ds, prog, nullptr, 0, list.data(), int64_t(list.size()), mc, ranges[size_t(me)],
+  int local = run_exact<T>(ctx, req, prog, list.data(), int64_t(list.size()), mc, ranges[size_t(me)],
                            reinterpret_cast<T*>(mine.data()));
   if (local != SR_OK) std::fill(mine.begin(), mine.end(), 0);
   const double err = local != SR_OK ? 1.0 : 0.0;
@@ -3492,14 +3468,14 @@ int gather_checked(sr_ctx* ctx, const void* payload, size_t bytes, int local, st
 // continuing from the previous shard's fold (one all-gather per rank; a rank's chain is O(1) per
 // segment but for the segments where the fold crosses a binade).  Collective; out = the folds (T).
 template <typename T>
-int fold_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, int loss_kind,
-                 const std::vector<int64_t>& list, std::vector<T>* out) {
+int fold_sharded(sr_ctx* ctx, const EvalReq& req, const std::vector<int64_t>& list, std::vector<T>* out) {
+  const sr_dataset* const ds = req.ds;
   out->assign(list.size(), T(0));
   if (list.empty()) return SR_OK;
   const int nr = ctx->comm_ranks, me = ctx->comm_rank;
   const std::vector<int64_t>& offs = ds->shard_offs;
   const int64_t n_total = offs[size_t(nr)];
-  if (nr == 1) return fold_exact<T>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, list, out);
+  if (nr == 1) return fold_exact<T>(ctx, req, n_total, list, out);
   int64_t max_rows = 0;
   for (int r = 0; r < nr; ++r) max_rows = std::max(max_rows, offs[size_t(r) + 1] - offs[size_t(r)]);
   const int64_t per = fold_batch_trees(max_rows, sizeof(T), false);  // the same cut on every rank
@@ -3511,7 +3487,6 @@ int fold_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_
   const int64_t seg_len = fold_seg_len(ctx, ds->n);
   const int64_t n_seg = seg_len > 0 ? (ds->n + seg_len - 1) / seg_len : 0;
   hipStream_t s = ctx->stream;
-  KeepCallInfo keep(ctx);
   std::vector<char> every;
   size_t slot = 0;
   int pending = SR_OK;  // a local failure after a gather: sent in the next one's error word
@@ -3519,8 +3494,7 @@ int fold_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_
     const size_t nb = std::min(list.size() - b0, size_t(per));
     // 1. this shard's predictions and segment sums; its per-tree total
     FoldDev<T> fd;
-    int local = fold_prepare<T>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, list.data() + b0, nb, seg_len,
-                                &fd);
+    int local = fold_prepare<T>(ctx, req, n_total, list.data() + b0, nb, seg_len, &fd);
     std::vector<double> tot(nb, 0.0);
     if (local == SR_OK && seg_len > 0) {
       std::vector<double> ss(nb * size_t(n_seg));
@@ -3549,7 +3523,7 @@ int fold_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_
       if (me == r && local == SR_OK && pending == SR_OK) {
         if (r > 0 && hipMemcpyAsync(fd.carry, carry.data(), nb * sizeof(T), hipMemcpyHostToDevice, s) != hipSuccess)
           local = set_error(SR_ERR_HIP, "fold: carry upload failed");
-        if (local == SR_OK) local = fold_finish<T>(ctx, ds, nullptr, 0, loss_kind, nb, seg_len, fd, true, r > 0, vals.data());
+        if (local == SR_OK) local = fold_finish<T>(ctx, req, nb, seg_len, fd, true, r > 0, vals.data());
       }
       rc = gather_checked(ctx, vals.data(), nb * sizeof(T), me == r ? local : SR_OK, &every, &slot, "the loss fold",
                           &pending);
@@ -3720,9 +3694,9 @@ int jl_wsum_sharded(sr_ctx* ctx, const sr_dataset* ds, T* out) {
 // order across the shards.  Every rank enters every collective, also after a local failure (its
 // partials zeroed, its error word set), and then every rank returns an error.
 template <typename T>
-int eval_sharded_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, int loss_kind,
-                      T* out_loss, uint8_t* out_complete) {
-  const int64_t nt = trees->n_trees;
+int eval_sharded_impl(sr_ctx* ctx, const EvalReq& req, T* out_loss, uint8_t* out_complete) {
+  const sr_dataset* const ds = req.ds;
+  const int64_t nt = req.trees->n_trees;
   const int nr = ctx->comm_ranks;
   const size_t n5 = size_t(5) * size_t(nt);
   // [5][nt] partials | error word, then the finalized losses (T) and complete codes
@@ -3746,12 +3720,13 @@ int eval_sharded_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_
   ctx->start_phases(t0);
   // 3. this shard
   SrProgramBatch<T> prog;
-  Grid g;
-  ctx->want_fold = true;  // (the in-order fold's steps and walks follow the ranks' agreement, step 6)
-  int local = nt > 0 ? run_batch<T>(ctx, ds, opset_id, trees, nullptr, 0, n_total, loss_kind, SR_MODE_LOSS, &prog, &g,
-                                    true, &sc)
-                     : SR_OK;
-  ctx->want_fold = false;
+  BatchWants want;
+  want.n_total = n_total;
+  want.allow_derived = true;
+  want.shard = &sc;
+  want.fold = true;  // (the in-order fold's steps and walks follow the ranks' agreement, step 6)
+  BatchResult res;
+  int local = nt > 0 ? run_batch<T>(ctx, req, want, &prog, &res) : SR_OK;
   hipStream_t s = ctx->stream;
   char* base = ctx->coll_packed.as<char>();
   double* dst = reinterpret_cast<double*>(base);
@@ -3807,7 +3782,7 @@ int eval_sharded_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_
   std::vector<uint8_t> list_ok;
   ctx->n_exact_last = int64_t(list.size());
   ctx->exact_kernel_ms = 0.0;
-  rc = exact_sharded<T>(ctx, ds, prog, list, &list_ok);
+  rc = exact_sharded<T>(ctx, req, prog, list, &list_ok);
   if (rc != SR_OK) return rc;
   for (size_t i = 0; i < list.size(); ++i) {
     const int64_t t = list[i];
@@ -3832,7 +3807,7 @@ int eval_sharded_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_
   ctx->fold_slow_last = ctx->fold_seg_last = 0;
   for (double& v : ctx->fold_ms) v = 0.0;
   std::vector<T> fold;
-  rc = fold_sharded<T>(ctx, ds, opset_id, trees, loss_kind, fold_list, &fold);
+  rc = fold_sharded<T>(ctx, req, fold_list, &fold);
   if (rc != SR_OK) return rc;
   // mean: total / count, in T; weighted: total / sum(w), the reference's pairwise Base.sum in T
   T fden = T(denom);
@@ -3870,8 +3845,8 @@ std::vector<int> tree_owners(const sr_tree_batch* trees, int nr) {
 // and ONE all-gather of every rank's results ([loss (T) | complete] of its trees, in tree order, and
 // an error word) hands every rank every result.
 template <typename T>
-int eval_tree_sharded_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, int loss_kind,
-                           T* out_loss, uint8_t* out_complete) {
+int eval_tree_sharded_impl(sr_ctx* ctx, const EvalReq& req, T* out_loss, uint8_t* out_complete) {
+  const sr_tree_batch* const trees = req.trees;
   const int64_t nt = trees->n_trees;
   const int nr = ctx->comm_ranks, me = ctx->comm_rank;
   const std::vector<int> owner = nr > 1 ? tree_owners(trees, nr) : std::vector<int>(size_t(nt), 0);
@@ -3895,10 +3870,12 @@ int eval_tree_sharded_impl(sr_ctx* ctx, const sr_dataset* ds, int opset_id, cons
     T* l = reinterpret_cast<T*>(hm);
     uint8_t* c = reinterpret_cast<uint8_t*>(hm + o_comp);
     if (nr == 1) {  // (one rank owns every tree, in order: no sub-batch)
-      local = eval_loss_impl<T>(ctx, ds, opset_id, trees, nullptr, 0, loss_kind, l, c);
+      local = eval_loss_impl<T>(ctx, req, l, c);
     } else {
       SubBatch<T> sub(*trees, mine.data(), mine.size());
-      local = eval_loss_impl<T>(ctx, ds, opset_id, &sub.b, nullptr, 0, loss_kind, l, c);
+      EvalReq mreq = req;
+      mreq.trees = &sub.b;
+      local = eval_loss_impl<T>(ctx, mreq, l, c);
     }
   }
   const double err = local != SR_OK ? 1.0 : 0.0;
@@ -4244,25 +4221,11 @@ int sr_dataset_denominator(const sr_dataset* ds, double* denom) {
   return SR_OK;
 }
 
-int sr_eval_loss_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                       const int64_t* row_idx, int64_t n_idx, int loss_kind, void* out_loss, uint8_t* out_complete) {
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_loss_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete);
-  return eval_loss_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete);
-}
-
-// The parametric entry points: the plain call with the batch's parameter side installed in the context
-// for its duration (run_batch and the passes after it read sr_ctx::param).
+// The eleven sr_eval_loss_batch* / sr_eval_grad_batch* / sr_eval_tree_array* entry points fill an EvalReq and
+// call eval_entry: the refusals in their order, the lock, the device, then the call for the dataset's type.
 namespace {
-struct ParamScope {
-  sr_ctx* ctx;
-  ParamScope(sr_ctx* c, const sr_param_batch* p) : ctx(c) { c->param = p; }
-  ~ParamScope() { ctx->param = nullptr; }
-};
+// a parametric call's batch against the dataset and the trees (the one copy of these checks: run_batch's
+// stage_param_table and eval_grad_impl rely on them)
 int check_params(const sr_dataset* ds, const sr_tree_batch* trees, const sr_param_batch* params) {
   if (!params) return set_error(SR_ERR_INVALID_ARG, "NULL parameter batch");
   if (ds->n_classes <= 0) return set_error(SR_ERR_INVALID_ARG, "a parametric call needs a dataset uploaded with classes");
@@ -4274,97 +4237,74 @@ int check_params(const sr_dataset* ds, const sr_tree_batch* trees, const sr_para
     return set_error(SR_ERR_INVALID_ARG, "sr_param_batch has NULL arrays");
   return SR_OK;
 }
+
+enum EvalKind { kEvalLoss, kEvalGrad, kEvalPred };
+
+// req: as the entry point filled it — `views` set by the _views variants (several row views in one call,
+// per-island minibatches; row_idx / n_idx then hold view_rows / view_len), `params` by the _parametric ones
+// (`parametric`: the variant takes a parameter batch, so a NULL one is refused).  out: the losses or the
+// predictions.
+int eval_entry(sr_ctx* ctx, EvalReq& req, EvalKind kind, bool parametric, void* out, void* out_grad, uint8_t* out_complete) {
+  if (parametric && kind != kEvalPred && req.loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
+  int rc = validate_common(ctx, req.ds, req.opset_id, req.trees);
+  if (rc != SR_OK) return rc;
+  if (parametric && (rc = check_params(req.ds, req.trees, req.params)) != SR_OK) return rc;
+  if (req.views && (req.views->n_views < 1 || req.views->view_len < 1 || !req.row_idx ||
+                    (req.trees->n_trees > 0 && !req.views->tree_view)))
+    return set_error(SR_ERR_INVALID_ARG, "bad row views");
+  if (kind == kEvalGrad) {
+    if (req.trees->n_trees > 0 && (!out || !out_grad || !out_complete))
+      return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
+    if (!req.ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
+  }
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  if (req.views && req.views->n_views == 1) req.views = nullptr;  // (one view: the plain gather path)
+  auto go = [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (kind == kEvalLoss) return eval_loss_impl<T>(ctx, req, out, out_complete);
+    if (kind == kEvalGrad) return eval_grad_impl<T>(ctx, req, out, out_grad, out_complete);
+    return eval_pred_impl<T>(ctx, req, out, out_complete);
+  };
+  return req.ds->dtype == SR_DTYPE_F32 ? go(float{}) : go(double{});
+}
 }  // namespace
+
+int sr_eval_loss_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                       const int64_t* row_idx, int64_t n_idx, int loss_kind, void* out_loss, uint8_t* out_complete) {
+  EvalReq req{ds, opset_id, trees, nullptr, row_idx, n_idx, nullptr, loss_kind};
+  return eval_entry(ctx, req, kEvalLoss, false, out_loss, nullptr, out_complete);
+}
 
 int sr_eval_loss_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                   const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind,
                                   void* out_loss, uint8_t* out_complete) {
-  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  ParamScope scope(ctx, params);
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_loss_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete);
-  return eval_loss_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_complete);
-}
-
-// several row views in one call (per-island minibatches): validated here, ViewSpec below the ABI
-static int check_views(const sr_tree_batch* trees, const int32_t* tree_view, int n_views, const int64_t* view_rows,
-                       int64_t view_len) {
-  if (n_views < 1 || view_len < 1 || !view_rows || (trees->n_trees > 0 && !tree_view))
-    return set_error(SR_ERR_INVALID_ARG, "bad row views");
-  return SR_OK;
+  EvalReq req{ds, opset_id, trees, params, row_idx, n_idx, nullptr, loss_kind};
+  return eval_entry(ctx, req, kEvalLoss, true, out_loss, nullptr, out_complete);
 }
 
 int sr_eval_loss_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                              const int32_t* tree_view, int n_views, const int64_t* view_rows, int64_t view_len,
                              int loss_kind, void* out_loss, uint8_t* out_complete) {
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if ((rc = check_views(trees, tree_view, n_views, view_rows, view_len)) != SR_OK) return rc;
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
   const ViewSpec vs{tree_view, n_views, view_len};
-  const ViewSpec* v = n_views > 1 ? &vs : nullptr;  // (one view: the plain gather path)
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_loss_impl<float>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
-  return eval_loss_impl<double>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
+  EvalReq req{ds, opset_id, trees, nullptr, view_rows, view_len, &vs, loss_kind};
+  return eval_entry(ctx, req, kEvalLoss, false, out_loss, nullptr, out_complete);
 }
 
 int sr_eval_loss_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                         const sr_param_batch* params, const int32_t* tree_view, int n_views,
                                         const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
                                         uint8_t* out_complete) {
-  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
-  if ((rc = check_views(trees, tree_view, n_views, view_rows, view_len)) != SR_OK) return rc;
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  ParamScope scope(ctx, params);
   const ViewSpec vs{tree_view, n_views, view_len};
-  const ViewSpec* v = n_views > 1 ? &vs : nullptr;
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_loss_impl<float>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
-  return eval_loss_impl<double>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_complete, v);
+  EvalReq req{ds, opset_id, trees, params, view_rows, view_len, &vs, loss_kind};
+  return eval_entry(ctx, req, kEvalLoss, true, out_loss, nullptr, out_complete);
 }
 
-int sr_eval_tree_array_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, void* out_pred,
-                                  uint8_t* out_complete) {
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  ParamScope scope(ctx, params);
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_pred_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, out_pred, out_complete);
-  return eval_pred_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, out_pred, out_complete);
-}
-
-int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                             const int32_t* tree_view, int n_views, const int64_t* view_rows, int64_t view_len,
-                             int loss_kind, void* out_loss, void* out_grad, uint8_t* out_complete) {
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if ((rc = check_views(trees, tree_view, n_views, view_rows, view_len)) != SR_OK) return rc;
-  if (trees->n_trees > 0 && (!out_loss || !out_grad || !out_complete))
-    return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
-  if (!ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  const ViewSpec vs{tree_view, n_views, view_len};
-  const ViewSpec* v = n_views > 1 ? &vs : nullptr;
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_grad_impl<float>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_grad,
-                                 out_complete, v);
-  return eval_grad_impl<double>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_grad,
-                                out_complete, v);
+int sr_eval_grad_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                       const int64_t* row_idx, int64_t n_idx, int loss_kind, void* out_loss, void* out_grad,
+                       uint8_t* out_complete) {
+  EvalReq req{ds, opset_id, trees, nullptr, row_idx, n_idx, nullptr, loss_kind};
+  return eval_entry(ctx, req, kEvalGrad, false, out_loss, out_grad, out_complete);
 }
 
 // Gradients of ParametricExpression trees: per tree [nc constants | K x C parameter entries, column-major]
@@ -4372,54 +4312,38 @@ int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, co
 int sr_eval_grad_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                   const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind,
                                   void* out_loss, void* out_grad, uint8_t* out_complete) {
-  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
-  if (trees->n_trees > 0 && (!out_loss || !out_grad || !out_complete))
-    return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
-  if (!ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  ParamScope scope(ctx, params);
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_grad_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_grad, out_complete);
-  return eval_grad_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_grad, out_complete);
+  EvalReq req{ds, opset_id, trees, params, row_idx, n_idx, nullptr, loss_kind};
+  return eval_entry(ctx, req, kEvalGrad, true, out_loss, out_grad, out_complete);
+}
+
+int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                             const int32_t* tree_view, int n_views, const int64_t* view_rows, int64_t view_len,
+                             int loss_kind, void* out_loss, void* out_grad, uint8_t* out_complete) {
+  const ViewSpec vs{tree_view, n_views, view_len};
+  EvalReq req{ds, opset_id, trees, nullptr, view_rows, view_len, &vs, loss_kind};
+  return eval_entry(ctx, req, kEvalGrad, false, out_loss, out_grad, out_complete);
 }
 
 int sr_eval_grad_batch_views_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                                         const sr_param_batch* params, const int32_t* tree_view, int n_views,
                                         const int64_t* view_rows, int64_t view_len, int loss_kind, void* out_loss,
                                         void* out_grad, uint8_t* out_complete) {
-  if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if ((rc = check_params(ds, trees, params)) != SR_OK) return rc;
-  if ((rc = check_views(trees, tree_view, n_views, view_rows, view_len)) != SR_OK) return rc;
-  if (trees->n_trees > 0 && (!out_loss || !out_grad || !out_complete))
-    return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
-  if (!ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  ParamScope scope(ctx, params);
   const ViewSpec vs{tree_view, n_views, view_len};
-  const ViewSpec* v = n_views > 1 ? &vs : nullptr;
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_grad_impl<float>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_grad,
-                                 out_complete, v);
-  return eval_grad_impl<double>(ctx, ds, opset_id, trees, view_rows, view_len, loss_kind, out_loss, out_grad,
-                                out_complete, v);
+  EvalReq req{ds, opset_id, trees, params, view_rows, view_len, &vs, loss_kind};
+  return eval_entry(ctx, req, kEvalGrad, true, out_loss, out_grad, out_complete);
 }
 
 int sr_eval_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                        const int64_t* row_idx, int64_t n_idx, void* out_pred, uint8_t* out_complete) {
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_pred_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, out_pred, out_complete);
-  return eval_pred_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, out_pred, out_complete);
+  EvalReq req{ds, opset_id, trees, nullptr, row_idx, n_idx, nullptr, SR_LOSS_L2DIST};
+  return eval_entry(ctx, req, kEvalPred, false, out_pred, nullptr, out_complete);
+}
+
+int sr_eval_tree_array_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                  const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, void* out_pred,
+                                  uint8_t* out_complete) {
+  EvalReq req{ds, opset_id, trees, params, row_idx, n_idx, nullptr, SR_LOSS_L2DIST};
+  return eval_entry(ctx, req, kEvalPred, true, out_pred, nullptr, out_complete);
 }
 
 int sr_eval_loss_partials(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
@@ -4432,9 +4356,12 @@ int sr_eval_loss_partials(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const
   if (n_total < ds->n) return set_error(SR_ERR_INVALID_ARG, "n_total smaller than this shard");
   Lock l(ctx);
   SR_HIP_CHECK(hipSetDevice(ctx->device));
-  Grid g;
+  const EvalReq req{ds, opset_id, trees, nullptr, nullptr, 0, nullptr, loss_kind};
+  BatchWants want;
+  want.n_total = n_total;
+  BatchResult res;
   auto t0 = std::chrono::steady_clock::now();
-  rc = run_batch_any(ctx, ds, opset_id, trees, n_total, loss_kind, &g);
+  rc = run_batch_any(ctx, req, want, &res);
   if (rc != SR_OK || nt == 0) return rc;
   hipStream_t s = ctx->stream;
   const hipMemcpyKind kind = out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -4456,9 +4383,12 @@ int sr_eval_loss_partials_packed(sr_ctx* ctx, const sr_dataset* ds, int opset_id
   if (n_total < ds->n) return set_error(SR_ERR_INVALID_ARG, "n_total smaller than this shard");
   Lock l(ctx);
   SR_HIP_CHECK(hipSetDevice(ctx->device));
-  Grid g;
+  const EvalReq req{ds, opset_id, trees, nullptr, nullptr, 0, nullptr, loss_kind};
+  BatchWants want;
+  want.n_total = n_total;
+  BatchResult res;
   auto t0 = std::chrono::steady_clock::now();
-  rc = run_batch_any(ctx, ds, opset_id, trees, n_total, loss_kind, &g);
+  rc = run_batch_any(ctx, req, want, &res);
   if (rc != SR_OK || nt == 0) return rc;
   hipStream_t s = ctx->stream;
   const size_t bytes = size_t(5) * size_t(nt) * sizeof(double);
@@ -4564,9 +4494,12 @@ int sr_eval_loss_partials_allreduce(sr_ctx* ctx, const sr_dataset* ds, int opset
   prep.need(ctx->coll_packed, (n + 1) * sizeof(double));
   rc = agree_prep(ctx, prep);
   if (rc != SR_OK) return rc;
-  Grid g;
+  const EvalReq req{ds, opset_id, trees, nullptr, nullptr, 0, nullptr, loss_kind};
+  BatchWants want;
+  want.n_total = n_total;
+  BatchResult res;
   auto t0 = std::chrono::steady_clock::now();
-  rc = run_batch_any(ctx, ds, opset_id, trees, n_total, loss_kind, &g);
+  rc = run_batch_any(ctx, req, want, &res);
   int local = rc;
   hipStream_t s = ctx->stream;
   double* dst = ctx->coll_packed.as<double>();
@@ -4600,9 +4533,10 @@ int sr_eval_loss_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const 
   if (!ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
   Lock l(ctx);
   SR_HIP_CHECK(hipSetDevice(ctx->device));
+  const EvalReq req{ds, opset_id, trees, nullptr, nullptr, 0, nullptr, loss_kind};
   if (ds->dtype == SR_DTYPE_F32)
-    return eval_sharded_impl<float>(ctx, ds, opset_id, trees, loss_kind, static_cast<float*>(out_loss), out_complete);
-  return eval_sharded_impl<double>(ctx, ds, opset_id, trees, loss_kind, static_cast<double*>(out_loss), out_complete);
+    return eval_sharded_impl<float>(ctx, req, static_cast<float*>(out_loss), out_complete);
+  return eval_sharded_impl<double>(ctx, req, static_cast<double*>(out_loss), out_complete);
 }
 
 int sr_eval_loss_tree_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
@@ -4616,9 +4550,10 @@ int sr_eval_loss_tree_sharded(sr_ctx* ctx, const sr_dataset* ds, int opset_id, c
   if (trees->n_trees > 0 && !trees->offsets) return set_error(SR_ERR_INVALID_ARG, "sr_tree_batch has NULL arrays");
   Lock l(ctx);
   SR_HIP_CHECK(hipSetDevice(ctx->device));
+  const EvalReq req{ds, opset_id, trees, nullptr, nullptr, 0, nullptr, loss_kind};
   if (ds->dtype == SR_DTYPE_F32)
-    return eval_tree_sharded_impl<float>(ctx, ds, opset_id, trees, loss_kind, static_cast<float*>(out_loss), out_complete);
-  return eval_tree_sharded_impl<double>(ctx, ds, opset_id, trees, loss_kind, static_cast<double*>(out_loss), out_complete);
+    return eval_tree_sharded_impl<float>(ctx, req, static_cast<float*>(out_loss), out_complete);
+  return eval_tree_sharded_impl<double>(ctx, req, static_cast<double*>(out_loss), out_complete);
 }
 
 int sr_comm_info(sr_ctx* ctx, int* nranks, int* rank, char* paths, int64_t capacity) {
@@ -4704,16 +4639,19 @@ int sr_jsum_partials(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_t
   if (n_list == 0 || max_checks == 0) return SR_OK;
   Lock l(ctx);
   SR_HIP_CHECK(hipSetDevice(ctx->device));
-  Grid g;
+  const EvalReq req{ds, opset_id, trees, nullptr, nullptr, 0, nullptr, SR_LOSS_L2DIST};
+  BatchWants want;
+  want.n_total = n_total;
+  BatchResult res;
   const std::vector<JlRange> ranges = jl_ranges(row_offset, ds->n, n_total);
   auto go = [&](auto tag) -> int {
     using T = decltype(tag);
     SrProgramBatch<T> prog;
-    int r = run_batch<T>(ctx, ds, opset_id, trees, nullptr, 0, n_total, SR_LOSS_L2DIST, SR_MODE_LOSS, &prog, &g);
+    int r = run_batch<T>(ctx, req, want, &prog, &res);
     if (r != SR_OK) return r;
     SR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (prog.max_checks > max_checks) return set_error(SR_ERR_INVALID_ARG, "max_checks too small");
-    return run_exact<T>(ctx, ds, prog, nullptr, 0, tree_list, n_list, max_checks, ranges, static_cast<T*>(out_vals));
+    return run_exact<T>(ctx, req, prog, tree_list, n_list, max_checks, ranges, static_cast<T*>(out_vals));
   };
   return ds->dtype == SR_DTYPE_F32 ? go(float{}) : go(double{});
 }
@@ -4751,21 +4689,6 @@ int sr_finalize_losses(int dtype, int64_t n_trees, const double* sums, const uin
   else
     return set_error(SR_ERR_INVALID_ARG, "unknown dtype");
   return SR_OK;
-}
-
-int sr_eval_grad_batch(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                       const int64_t* row_idx, int64_t n_idx, int loss_kind, void* out_loss, void* out_grad,
-                       uint8_t* out_complete) {
-  int rc = validate_common(ctx, ds, opset_id, trees);
-  if (rc != SR_OK) return rc;
-  if (trees->n_trees > 0 && (!out_loss || !out_grad || !out_complete))
-    return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
-  if (!ds->y) return set_error(SR_ERR_INVALID_ARG, "dataset has no y");
-  Lock l(ctx);
-  SR_HIP_CHECK(hipSetDevice(ctx->device));
-  if (ds->dtype == SR_DTYPE_F32)
-    return eval_grad_impl<float>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_grad, out_complete);
-  return eval_grad_impl<double>(ctx, ds, opset_id, trees, row_idx, n_idx, loss_kind, out_loss, out_grad, out_complete);
 }
 
 static int compile_info_impl(int dtype, int n_unary, const char* const* unary_names, int n_binary,
@@ -4877,8 +4800,8 @@ static void settle_timing(sr_ctx* ctx) {
   ctx->last_eval_ms = chunk_kernel_ms(ctx);
   ctx->last_busy_ms = chunk_busy_ms(ctx);
   ctx->fold_kernel_ms_last = 0.0;
-  if (ctx->fold_timed_last)
-    for (int c = 0; c < ctx->n_chunks_last; ++c) {
+  if (ctx->last.fold_timed)
+    for (int c = 0; c < ctx->last.n_chunks; ++c) {
       float m = 0.f;
       if (hipEventElapsedTime(&m, ctx->ev_fc0[c], ctx->ev_fc1[c]) == hipSuccess) ctx->fold_kernel_ms_last += double(m);
     }
@@ -4889,60 +4812,60 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n) {
   Lock l(ctx);
   if (n > 8) settle_timing(ctx);
   for (int i = 0; i < n && i < 5; ++i) out[i] = ctx->phase_ms[i];
-  if (n > 5) out[5] = double(ctx->n_chunks_last);
+  if (n > 5) out[5] = double(ctx->last.n_chunks);
   if (n > 6) out[6] = ctx->exact_kernel_ms;
-  if (n > 7) out[7] = double(ctx->rows_last);
+  if (n > 7) out[7] = double(ctx->last.rows);
   if (n > 8) out[8] = ctx->last_busy_ms;
   if (n > 9) out[9] = double(ctx->n_fold_last);
   if (n > 10) out[10] = double(ctx->fold_slow_last);
   if (n > 11) out[11] = double(ctx->fold_seg_last);
   for (int i = 0; i < 4; ++i)
     if (n > 12 + i) out[12 + i] = ctx->fold_ms[i];
-  if (n > 16 && !ctx->loss_list_read) {  // (the last call's listed loss launches: their counters, read once)
+  if (n > 16 && !ctx->last.loss_list_read) {  // (the last call's listed loss launches: their counters, read once)
     int32_t h[kMaxChunks * kLossListCnt] = {};
     SR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->stream2) SR_HIP_CHECK(hipStreamSynchronize(ctx->stream2));
-    SR_HIP_CHECK(hipMemcpy(h, ctx->loss_list.as<char>() + sr_loss_list_cnt_off(ctx->loss_list_nt_last), sizeof(h),
+    SR_HIP_CHECK(hipMemcpy(h, ctx->loss_list.as<char>() + sr_loss_list_cnt_off(ctx->last.loss_list_nt), sizeof(h),
                            hipMemcpyDeviceToHost));
     for (int c = 0; c < kMaxChunks; ++c) {
-      if (ctx->loss_listed_np[c] <= 0) continue;
-      ++ctx->n_loss_listed_launches_last;
-      ctx->n_loss_live_last += h[c * kLossListCnt];
-      ctx->n_loss_excl_last += ctx->loss_listed_np[c] - h[c * kLossListCnt];
+      if (ctx->last.loss_listed_np[c] <= 0) continue;
+      ++ctx->last.n_loss_listed_launches;
+      ctx->last.n_loss_live += h[c * kLossListCnt];
+      ctx->last.n_loss_excl += ctx->last.loss_listed_np[c] - h[c * kLossListCnt];
     }
-    ctx->loss_list_read = true;
+    ctx->last.loss_list_read = true;
   }
-  if (n > 16) out[16] = double(ctx->n_loss_listed_launches_last);
-  if (n > 17) out[17] = double(ctx->n_loss_live_last);
-  if (n > 18) out[18] = double(ctx->n_loss_excl_last);
+  if (n > 16) out[16] = double(ctx->last.n_loss_listed_launches);
+  if (n > 17) out[17] = double(ctx->last.n_loss_live);
+  if (n > 18) out[18] = double(ctx->last.n_loss_excl);
   // the last call's compacted FOLD launches, region r (sr_fold_region: 2 chunk, + 1 for the LDS-stack launch) at
   // out[19 + 4 r ..]: {live workgroups, listed entries, entries per workgroup g, the longest row block's list};
   // zeros for a region without such a launch
-  if (n > 19 && !ctx->fold_wg_read) {
+  if (n > 19 && !ctx->last.fold_wg_read) {
     SR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->stream2) SR_HIP_CHECK(hipStreamSynchronize(ctx->stream2));
-    std::vector<int32_t> h(sr_fold_wg_words(ctx->fold_wg_stride_rb));
+    std::vector<int32_t> h(sr_fold_wg_words(ctx->last.fold_wg_stride_rb));
     SR_HIP_CHECK(hipMemcpy(h.data(), ctx->fold_wg.p, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int r = 0; r < 2 * kMaxChunks; ++r) {
-      const int nrb = ctx->fold_wg_nrb[r];
+      const int nrb = ctx->last.fold_wg_nrb[r];
       if (nrb <= 0) continue;
-      const int32_t* cnt = h.data() + sr_fold_wg_off(r, ctx->fold_wg_stride_rb);
-      const int32_t* wg0 = cnt + ctx->fold_wg_stride_rb;
+      const int32_t* cnt = h.data() + sr_fold_wg_off(r, ctx->last.fold_wg_stride_rb);
+      const int32_t* wg0 = cnt + ctx->last.fold_wg_stride_rb;
       int64_t entries = 0, longest = 0;
       for (int b = 0; b < nrb; ++b) {
         entries += cnt[b];
         longest = std::max<int64_t>(longest, cnt[b]);
       }
-      ctx->fold_wg_info[r][0] = double(wg0[nrb]);
-      ctx->fold_wg_info[r][1] = double(entries);
-      ctx->fold_wg_info[r][2] = double(wg0[nrb + 1]);
-      ctx->fold_wg_info[r][3] = double(longest);
+      ctx->last.fold_wg_info[r][0] = double(wg0[nrb]);
+      ctx->last.fold_wg_info[r][1] = double(entries);
+      ctx->last.fold_wg_info[r][2] = double(wg0[nrb + 1]);
+      ctx->last.fold_wg_info[r][3] = double(longest);
     }
-    ctx->fold_wg_read = true;
+    ctx->last.fold_wg_read = true;
   }
   for (int r = 0; r < 2 * kMaxChunks; ++r)
     for (int k = 0; k < 4; ++k)
-      if (n > 19 + 4 * r + k) out[19 + 4 * r + k] = ctx->fold_wg_info[r][k];
+      if (n > 19 + 4 * r + k) out[19 + 4 * r + k] = ctx->last.fold_wg_info[r][k];
   return SR_OK;
 }
 
@@ -4970,7 +4893,7 @@ int sr_last_grad_info(sr_ctx* ctx, int n, double* kernel_ms, double* flops, int6
 
 int sr_tuning_info(sr_ctx* ctx, int* used_derived_columns, int64_t* exact_trees) {
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
-  if (used_derived_columns) *used_derived_columns = ctx->n_derived_last;
+  if (used_derived_columns) *used_derived_columns = ctx->last.n_derived;
   if (exact_trees) *exact_trees = ctx->n_exact_last;
   return SR_OK;
 }
@@ -4979,7 +4902,7 @@ int sr_ref_fold_info(sr_ctx* ctx, int* path, int64_t* n_folded, int64_t* n_fallb
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
   Lock l(ctx);
   settle_timing(ctx);
-  if (path) *path = ctx->fold_path_last;
+  if (path) *path = ctx->last.fold_path;
   if (n_folded) *n_folded = ctx->n_ref_ok_last;
   if (n_fallback) *n_fallback = ctx->n_ref_fail_last;
   if (fold_kernel_ms) *fold_kernel_ms = ctx->fold_kernel_ms_last;
@@ -4989,17 +4912,17 @@ int sr_ref_fold_info(sr_ctx* ctx, int* path, int64_t* n_folded, int64_t* n_fallb
 int sr_last_fold_cand(sr_ctx* ctx, int64_t* taken, int64_t* rerun) {
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
   Lock l(ctx);
-  if (!ctx->fold_cand_read) {  // (the plan's counters of the last FOLD-mode call, read once)
+  if (!ctx->last.fold_cand_read) {  // (the plan's counters of the last FOLD-mode call, read once)
     int h[4] = {0, 0, 0, 0};
     SR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->stream2) SR_HIP_CHECK(hipStreamSynchronize(ctx->stream2));
     SR_HIP_CHECK(hipMemcpy(h, ctx->fold_ctl.p, sizeof(h), hipMemcpyDeviceToHost));
-    ctx->n_cand_taken_last = h[1];
-    ctx->n_cand_rerun_last = h[2];
-    ctx->fold_cand_read = true;
+    ctx->last.n_cand_taken = h[1];
+    ctx->last.n_cand_rerun = h[2];
+    ctx->last.fold_cand_read = true;
   }
-  if (taken) *taken = ctx->n_cand_taken_last;
-  if (rerun) *rerun = ctx->n_cand_rerun_last;
+  if (taken) *taken = ctx->last.n_cand_taken;
+  if (rerun) *rerun = ctx->last.n_cand_rerun;
   return SR_OK;
 }
 
