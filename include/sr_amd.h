@@ -219,7 +219,7 @@ int sr_eval_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr
  * own matrix: results do not depend on the other trees of the batch.  The deferred validity checks bound
  * leaf values by max(max|X|, max|parameters|) over the call (Inf when an entry is non-finite, used by a row
  * or not); such a call runs the per-node-check kernels.  Parametric calls run their own, smaller set of
- * kernel builds (csrc/sr_inst_*param*.hip): of the tuning knobs, "rows_per_lane" only chooses between the
+ * kernel builds (SR_TIER_PARAM, csrc/sr_builds.h): of the tuning knobs, "rows_per_lane" only chooses between the
  * classic build and the one register-stack build per type, the 8-wave build and derived columns are not
  * used; results do not depend on either.
  */

@@ -1509,7 +1509,7 @@ hipError_t sr_launch_fold_walk(SrFoldTabs ft, const SrFoldWho& who, int np, int 
                        all_rows);
   return hipGetLastError();
 }
-#define SR_INSTANTIATE_FOLD2(T)                                                                                      \
+#define SR_FOLD2_LAUNCHERS(T)                                                                                      \
   template hipError_t sr_launch_fold_plan<T>(const double*, int, int, const uint32_t*, const SrFoldWho&, double,   \
                                              SrFoldTabs, int*, int, const int4*, hipStream_t);                        \
   template hipError_t sr_launch_fold_stab<T>(const double*, int, int, int64_t, int64_t, const uint32_t*,              \
@@ -1517,8 +1517,8 @@ hipError_t sr_launch_fold_walk(SrFoldTabs ft, const SrFoldWho& who, int np, int 
                                              const uint8_t*, double*, uint32_t*, hipStream_t);                         \
   template hipError_t sr_launch_fold_walk<T>(SrFoldTabs, const SrFoldWho&, int, int, int64_t, int64_t, const T*,      \
                                              int64_t, const uint32_t*, const T*, T*, int32_t*, void*, int, hipStream_t);
-SR_INSTANTIATE_FOLD2(float)
-SR_INSTANTIATE_FOLD2(double)
+SR_FOLD2_LAUNCHERS(float)
+SR_FOLD2_LAUNCHERS(double)
 
 // Julia [nf, n] column-major -> per-feature rows [nf][ld]; padded rows replicate row 0 so that the
 // interpreter's validity checks never see a value that is not in the dataset.
@@ -1563,194 +1563,38 @@ hipError_t sr_launch_pad(T* v, int64_t n, int64_t ld, T pad_value, int replicate
   return hipGetLastError();
 }
 
-// BASIC-tier loss kernels are built per elementwise loss (the loss code folds away).
-template <typename T, int R, bool GATHER, bool VSTK = false>
-hipError_t sr_launch_basic_loss(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s) {
-  if (a.loss_kind == SR_LOSS_L1)
-    return sr_launch_tile<T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, SR_LOSS_L1, VSTK>(a, n_blocks, s);
-  if (a.loss_kind == SR_LOSS_L2)
-    return sr_launch_tile<T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, SR_LOSS_L2, VSTK>(a, n_blocks, s);
-  return sr_launch_tile<T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, -1, VSTK>(a, n_blocks, s);  // other losses
+// The launcher table: every row of sr_builds.h with the pointer to its sr_launch_tile, per element type (a
+// row of the other type keeps a null pointer).  Only the declaration of sr_launch_tile is visible here: the
+// instantiations are sr_inst.hip's, so a row without one is an undefined symbol, never a kernel compiled here.
+template <typename T>
+struct SrBuildLauncher {
+  SrBuildKey key;
+  hipError_t (*fn)(const SrEvalArgs<T>&, int, hipStream_t);
+};
+template <typename T, typename U, int R, int MODE, bool GATHER, int TIER, int W, int LK, bool VSTK>
+constexpr SrBuildLauncher<T> sr_build_launcher() {
+  if constexpr (sizeof(T) == sizeof(U))
+    return {sr_build_key(int(sizeof(U)), R, MODE, GATHER, TIER, W, LK, VSTK), &sr_launch_tile<U, R, MODE, GATHER, TIER, W, LK, VSTK>};
+  else
+    return {SrBuildKey{}, nullptr};
 }
+#define SR_LAUNCHER_ROW(U, R, MODE, GATHER, TIER, W, LK, VSTK) sr_build_launcher<T, U, R, MODE, GATHER, TIER, W, LK, VSTK>(),
 
 template <typename T>
-hipError_t sr_launch_loss_cand(const SrEvalArgs<T>& a, int R, int waves, int n_blocks, hipStream_t s) {
-  if constexpr (sizeof(T) == 4) {  // (sr_inst_f32_cand.hip)
-    if (R != 16 || waves != 4 || a.fold_cand == nullptr) return hipErrorInvalidValue;
-    return a.loss_kind == SR_LOSS_L2
-               ? sr_launch_tile<T, 16, SR_MODE_LOSS, false, SR_TIER_BASIC | SR_TIER_CAND, 4, SR_LOSS_L2, true>(a, n_blocks, s)
-               : sr_launch_tile<T, 16, SR_MODE_LOSS, false, SR_TIER_BASIC | SR_TIER_CAND, 4, -1, true>(a, n_blocks, s);
-  } else {
-    return hipErrorInvalidValue;
-  }
-}
-template hipError_t sr_launch_loss_cand<float>(const SrEvalArgs<float>&, int, int, int, hipStream_t);
-template hipError_t sr_launch_loss_cand<double>(const SrEvalArgs<double>&, int, int, int, hipStream_t);
-
-// The kernels of expression-loss calls (sr_inst_*lossx*.hip): the classic kernel at its default rows per
-// lane, 4 waves, full view or gathered, per tier.
-template <typename T>
-hipError_t sr_launch_eval_lossx(const SrEvalArgs<T>& a, bool gather, int tier, int R, int waves, bool vstk, int n_blocks,
-                                hipStream_t s) {
-  constexpr int RB = sizeof(T) == 4 ? 8 : 4;  // BASIC classic rows per lane
-  constexpr int RF = sizeof(T) == 4 ? 4 : 2;  // FULL tier rows per lane
-  if (a.loss_kind != SR_LOSS_EXPR || a.lx_code == nullptr || a.lx_n < 1 || a.lx_n > SR_LX_MAX_INS) return hipErrorInvalidValue;
-  if (vstk || waves != 4) return hipErrorInvalidValue;
-  if (tier == SR_TIER_BASIC) {
-    if (R != RB) return hipErrorInvalidValue;
-    return gather ? sr_launch_tile<T, RB, SR_MODE_LOSS, true, SR_TIER_BASIC, 4, SR_LOSS_EXPR>(a, n_blocks, s)
-                  : sr_launch_tile<T, RB, SR_MODE_LOSS, false, SR_TIER_BASIC, 4, SR_LOSS_EXPR>(a, n_blocks, s);
-  }
-  if (R != RF) return hipErrorInvalidValue;
-  return gather ? sr_launch_tile<T, RF, SR_MODE_LOSS, true, SR_TIER_FULL, 4, SR_LOSS_EXPR>(a, n_blocks, s)
-                : sr_launch_tile<T, RF, SR_MODE_LOSS, false, SR_TIER_FULL, 4, SR_LOSS_EXPR>(a, n_blocks, s);
-}
-template hipError_t sr_launch_eval_lossx<float>(const SrEvalArgs<float>&, bool, int, int, int, bool, int, hipStream_t);
-template hipError_t sr_launch_eval_lossx<double>(const SrEvalArgs<double>&, bool, int, int, int, bool, int, hipStream_t);
-
-template <typename T>
-hipError_t sr_launch_eval(const SrEvalArgs<T>& a, int mode, bool gather, int tier, int R, int waves, bool vstk,
-                          int n_blocks, hipStream_t s) {
-  // an expression loss: its own builds or an error, never a generic-loss kernel (whose default case is L2)
-  if (a.loss_kind == SR_LOSS_EXPR && mode == SR_MODE_LOSS) return sr_launch_eval_lossx<T>(a, gather, tier, R, waves, vstk, n_blocks, s);
-  if (a.loss_kind == SR_LOSS_EXPR && mode == SR_MODE_FOLD) return hipErrorInvalidValue;
-  if constexpr (sizeof(T) == 4) {
-    if (mode == SR_MODE_FOLD) {  // (the launch shapes of the loss launches a large call runs: sr_inst_f32_fold*.hip)
-      const bool l2 = a.loss_kind == SR_LOSS_L2;
-      if (vstk) {
-        if (tier != SR_TIER_BASIC || gather || R != 16) return hipErrorInvalidValue;
-        return l2 ? sr_launch_tile<T, 16, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, SR_LOSS_L2, true>(a, n_blocks, s)
-                  : sr_launch_tile<T, 16, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, -1, true>(a, n_blocks, s);
-      }
-      if (tier == SR_TIER_BASIC) {
-        if (R != 8 || waves != 4) return hipErrorInvalidValue;
-        if (gather) return sr_launch_tile<T, 8, SR_MODE_FOLD, true, SR_TIER_BASIC, 4, -1>(a, n_blocks, s);
-        return l2 ? sr_launch_tile<T, 8, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, SR_LOSS_L2>(a, n_blocks, s)
-                  : sr_launch_tile<T, 8, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, -1>(a, n_blocks, s);
-      }
-      if (R != 4) return hipErrorInvalidValue;
-      return gather ? sr_launch_tile<T, 4, SR_MODE_FOLD, true, SR_TIER_FULL>(a, n_blocks, s)
-                    : sr_launch_tile<T, 4, SR_MODE_FOLD, false, SR_TIER_FULL>(a, n_blocks, s);
-    }
-    if (vstk) {
-      if (mode != SR_MODE_LOSS || tier != SR_TIER_BASIC || gather) return hipErrorInvalidValue;
-      if (R == 32) return sr_launch_basic_loss<T, 32, false, true>(a, n_blocks, s);
-      if (R == 16) return sr_launch_basic_loss<T, 16, false, true>(a, n_blocks, s);
-      if (R == 8) return sr_launch_basic_loss<T, 8, false, true>(a, n_blocks, s);
-      return hipErrorInvalidValue;
-    }
-    if (mode == SR_MODE_LOSS) {
-      if (tier == SR_TIER_BASIC) {
-        if (gather) return sr_launch_basic_loss<T, 8, true>(a, n_blocks, s);
-        if (R == 16) return sr_launch_basic_loss<T, 16, false>(a, n_blocks, s);
-        if (R == 4) return sr_launch_tile<T, 4, SR_MODE_LOSS, false, SR_TIER_BASIC>(a, n_blocks, s);
-        if (waves == 8 && a.loss_kind == SR_LOSS_L2)
-          return sr_launch_tile<T, 8, SR_MODE_LOSS, false, SR_TIER_BASIC, 8, SR_LOSS_L2>(a, n_blocks, s);
-        return sr_launch_basic_loss<T, 8, false>(a, n_blocks, s);
-      }
-      return gather ? sr_launch_tile<T, 4, SR_MODE_LOSS, true, SR_TIER_FULL>(a, n_blocks, s)
-                    : sr_launch_tile<T, 4, SR_MODE_LOSS, false, SR_TIER_FULL>(a, n_blocks, s);
-    }
-    if (mode == SR_MODE_PRED)
-      return gather ? sr_launch_tile<T, 4, SR_MODE_PRED, true, SR_TIER_FULL>(a, n_blocks, s)
-                    : sr_launch_tile<T, 4, SR_MODE_PRED, false, SR_TIER_FULL>(a, n_blocks, s);
-    if (tier == SR_TIER_BASIC) {  // (EXACT over a BASIC operator set: the smaller dispatch)
-      if (waves == 4)
-        return gather ? sr_launch_tile<T, 4, SR_MODE_EXACT, true, SR_TIER_BASIC, 4>(a, n_blocks, s)
-                      : sr_launch_tile<T, 4, SR_MODE_EXACT, false, SR_TIER_BASIC, 4>(a, n_blocks, s);
-      return gather ? sr_launch_tile<T, 4, SR_MODE_EXACT, true, SR_TIER_BASIC, 1>(a, n_blocks, s)
-                    : sr_launch_tile<T, 4, SR_MODE_EXACT, false, SR_TIER_BASIC, 1>(a, n_blocks, s);
-    }
-    if (waves == 4)  // (EXACT: 1 or 4 waves per workgroup, sharing the staged rows)
-      return gather ? sr_launch_tile<T, 4, SR_MODE_EXACT, true, SR_TIER_FULL, 4>(a, n_blocks, s)
-                    : sr_launch_tile<T, 4, SR_MODE_EXACT, false, SR_TIER_FULL, 4>(a, n_blocks, s);
-    return gather ? sr_launch_tile<T, 4, SR_MODE_EXACT, true, SR_TIER_FULL, 1>(a, n_blocks, s)
-                  : sr_launch_tile<T, 4, SR_MODE_EXACT, false, SR_TIER_FULL, 1>(a, n_blocks, s);
-  } else {
-    if (mode == SR_MODE_FOLD) return hipErrorInvalidValue;  // (Float64: small calls only, from stored losses)
-    if (vstk) {
-      if (mode != SR_MODE_LOSS || tier != SR_TIER_BASIC || gather) return hipErrorInvalidValue;
-      if (R == 8) return sr_launch_basic_loss<T, 8, false, true>(a, n_blocks, s);
-      if (R == 4) return sr_launch_basic_loss<T, 4, false, true>(a, n_blocks, s);
-      return hipErrorInvalidValue;
-    }
-    if (mode == SR_MODE_LOSS) {
-      if (tier == SR_TIER_BASIC)
-        return gather ? sr_launch_basic_loss<T, 4, true>(a, n_blocks, s) : sr_launch_basic_loss<T, 4, false>(a, n_blocks, s);
-      return gather ? sr_launch_tile<T, 2, SR_MODE_LOSS, true, SR_TIER_FULL>(a, n_blocks, s)
-                    : sr_launch_tile<T, 2, SR_MODE_LOSS, false, SR_TIER_FULL>(a, n_blocks, s);
-    }
-    if (mode == SR_MODE_PRED)
-      return gather ? sr_launch_tile<T, 2, SR_MODE_PRED, true, SR_TIER_FULL>(a, n_blocks, s)
-                    : sr_launch_tile<T, 2, SR_MODE_PRED, false, SR_TIER_FULL>(a, n_blocks, s);
-    if (tier == SR_TIER_BASIC) {
-      if (waves == 4)
-        return gather ? sr_launch_tile<T, 2, SR_MODE_EXACT, true, SR_TIER_BASIC, 4>(a, n_blocks, s)
-                      : sr_launch_tile<T, 2, SR_MODE_EXACT, false, SR_TIER_BASIC, 4>(a, n_blocks, s);
-      return gather ? sr_launch_tile<T, 2, SR_MODE_EXACT, true, SR_TIER_BASIC, 1>(a, n_blocks, s)
-                    : sr_launch_tile<T, 2, SR_MODE_EXACT, false, SR_TIER_BASIC, 1>(a, n_blocks, s);
-    }
-    if (waves == 4)
-      return gather ? sr_launch_tile<T, 2, SR_MODE_EXACT, true, SR_TIER_FULL, 4>(a, n_blocks, s)
-                    : sr_launch_tile<T, 2, SR_MODE_EXACT, false, SR_TIER_FULL, 4>(a, n_blocks, s);
-    return gather ? sr_launch_tile<T, 2, SR_MODE_EXACT, true, SR_TIER_FULL, 1>(a, n_blocks, s)
-                  : sr_launch_tile<T, 2, SR_MODE_EXACT, false, SR_TIER_FULL, 1>(a, n_blocks, s);
-  }
-}
-template hipError_t sr_launch_eval<float>(const SrEvalArgs<float>&, int, bool, int, int, int, bool, int, hipStream_t);
-template hipError_t sr_launch_eval<double>(const SrEvalArgs<double>&, int, bool, int, int, int, bool, int, hipStream_t);
-
-// The kernels of parametric calls (sr_inst_*param*.hip): the L2 and generic-loss builds only (L1 runs
-// the generic one), 4 waves everywhere, FOLD with the generic loss, EXACT in its FULL-tier build.
-template <typename T, int R, bool VSTK>
-static hipError_t sr_launch_param_basic_loss(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int n_blocks, hipStream_t s) {
-  if (a.loss_kind == SR_LOSS_L2)
-    return sr_launch_tile_param<T, R, SR_MODE_LOSS, false, SR_TIER_BASIC, 4, SR_LOSS_L2, VSTK>(a, p, n_blocks, s);
-  return sr_launch_tile_param<T, R, SR_MODE_LOSS, false, SR_TIER_BASIC, 4, -1, VSTK>(a, p, n_blocks, s);
-}
-template <typename T>
-hipError_t sr_launch_eval_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int mode, bool gather, int tier, int R,
-                                int waves, bool vstk, int n_blocks, hipStream_t s) {
-  constexpr int RB = sizeof(T) == 4 ? 8 : 4;   // BASIC classic rows per lane
-  constexpr int RV = sizeof(T) == 4 ? 16 : 8;  // BASIC register-stack rows per lane
-  constexpr int RF = sizeof(T) == 4 ? 4 : 2;   // FULL tier / PRED / EXACT rows per lane
-  if (waves != 4) return hipErrorInvalidValue;
-  if (mode == SR_MODE_LOSS && tier == SR_TIER_BASIC) {
-    if (vstk) return (R == RV && !gather) ? sr_launch_param_basic_loss<T, RV, true>(a, p, n_blocks, s) : hipErrorInvalidValue;
-    if (R != RB) return hipErrorInvalidValue;
-    if (gather) return sr_launch_tile_param<T, RB, SR_MODE_LOSS, true, SR_TIER_BASIC, 4, -1, false>(a, p, n_blocks, s);
-    return sr_launch_param_basic_loss<T, RB, false>(a, p, n_blocks, s);
-  }
-  if (mode == SR_MODE_FOLD) {
-    if constexpr (sizeof(T) == 4) {
-      if (tier == SR_TIER_BASIC) {
-        if (vstk)
-          return (R == RV && !gather) ? sr_launch_tile_param<T, RV, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, -1, true>(a, p, n_blocks, s)
-                                      : hipErrorInvalidValue;
-        if (R != RB) return hipErrorInvalidValue;
-        return gather ? sr_launch_tile_param<T, RB, SR_MODE_FOLD, true, SR_TIER_BASIC, 4, -1, false>(a, p, n_blocks, s)
-                      : sr_launch_tile_param<T, RB, SR_MODE_FOLD, false, SR_TIER_BASIC, 4, -1, false>(a, p, n_blocks, s);
-      }
-      if (vstk || R != RF) return hipErrorInvalidValue;
-      return gather ? sr_launch_tile_param<T, RF, SR_MODE_FOLD, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
-                    : sr_launch_tile_param<T, RF, SR_MODE_FOLD, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
-    }
-    return hipErrorInvalidValue;  // (Float64: small calls only, from stored losses)
-  }
-  if (vstk || R != RF) return hipErrorInvalidValue;
-  if (mode == SR_MODE_LOSS)
-    return gather ? sr_launch_tile_param<T, RF, SR_MODE_LOSS, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
-                  : sr_launch_tile_param<T, RF, SR_MODE_LOSS, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
-  if (mode == SR_MODE_PRED)
-    return gather ? sr_launch_tile_param<T, RF, SR_MODE_PRED, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
-                  : sr_launch_tile_param<T, RF, SR_MODE_PRED, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
-  if (mode == SR_MODE_EXACT)
-    return gather ? sr_launch_tile_param<T, RF, SR_MODE_EXACT, true, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s)
-                  : sr_launch_tile_param<T, RF, SR_MODE_EXACT, false, SR_TIER_FULL, 4, -1, false>(a, p, n_blocks, s);
+hipError_t sr_launch_eval(const SrEvalArgs<T>& a, const SrBuildRequest& req, int n_blocks, hipStream_t s) {
+  static constexpr SrBuildLauncher<T> launchers[] = {SR_ALL_BUILDS(SR_LAUNCHER_ROW)};
+  if (req.elem_size != int(sizeof(T)) || req.loss_kind != a.loss_kind) return hipErrorInvalidValue;
+  const SrBuildKey key = sr_resolve_build(req);
+  if (!key.ok()) return hipErrorInvalidValue;
+  // what the resolved build reads beyond the common arguments (SR_TIER_PARAM's table: sr_launch_tile)
+  if ((key.tier() & SR_TIER_CAND) && a.fold_cand == nullptr) return hipErrorInvalidValue;
+  if (key.lk() == SR_LOSS_EXPR && (a.lx_code == nullptr || a.lx_n < 1 || a.lx_n > SR_LX_MAX_INS)) return hipErrorInvalidValue;
+  for (const SrBuildLauncher<T>& row : launchers)  // (a call makes a handful of launches)
+    if (row.key == key && row.fn) return row.fn(a, n_blocks, s);
   return hipErrorInvalidValue;
 }
-template hipError_t sr_launch_eval_param<float>(const SrEvalArgs<float>&, const SrParamArgs<float>&, int, bool, int, int, int, bool, int, hipStream_t);
-template hipError_t sr_launch_eval_param<double>(const SrEvalArgs<double>&, const SrParamArgs<double>&, int, bool, int, int, int, bool, int, hipStream_t);
+template hipError_t sr_launch_eval<float>(const SrEvalArgs<float>&, const SrBuildRequest&, int, hipStream_t);
+template hipError_t sr_launch_eval<double>(const SrEvalArgs<double>&, const SrBuildRequest&, int, hipStream_t);
 template hipError_t sr_launch_transpose<float>(const float*, int64_t, int64_t, int64_t, float*, hipStream_t);
 template hipError_t sr_launch_transpose<double>(const double*, int64_t, int64_t, int64_t, double*, hipStream_t);
 template hipError_t sr_launch_pad<float>(float*, int64_t, int64_t, float, int, hipStream_t);

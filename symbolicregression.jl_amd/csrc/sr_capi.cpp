@@ -509,8 +509,7 @@ inline int check_loss_expr_weights(const sr_ctx::LossExpr* e, const sr_dataset* 
 // per-tree arrays are chunk-local), grid and kernel build.
 template <typename T>
 struct FoldRegion {
-  SrEvalArgs<T> a;
-  SrParamArgs<T> p;  // (a parametric call's second argument block; ptab NULL otherwise)
+  SrEvalArgs<T> a;  // (a parametric call's: ptab set)
   int64_t t0, pos0, np, n_blocks;
   int Rc;
   bool vstk;
@@ -605,7 +604,7 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
   fa.fold_wg0 = nullptr;
   // the compacted launch (sr_ctx::fold_compact): plain single-GPU calls over the full view; the grid stays the
   // region's (an upper bound: the list's workgroups come first, the rest return at once)
-  if (ctx->fold_compact && fr.idx >= 0 && !fr.p.ptab && !job.gather && fr.a.segs == nullptr && who.elig == nullptr &&
+  if (ctx->fold_compact && fr.idx >= 0 && !fr.a.ptab && !job.gather && fr.a.segs == nullptr && who.elig == nullptr &&
       who.est == nullptr) {
     int32_t* cnt = ctx->fold_wg.as<int32_t>() + sr_fold_wg_off(fr.idx, job.n_rb);
     int32_t* wg0 = cnt + job.n_rb;
@@ -620,10 +619,10 @@ int fold_steps(sr_ctx* ctx, const FoldJob<T>& job, const FoldRegion<T>& fr, SrFo
     fa.fold_wg0 = wg0;
     fa.code_lds = 0;  // (a listed workgroup's programs are no contiguous span: no LDS program cache)
   }
-  if (fr.p.ptab)  // (a parametric call's launches: the PARAM builds)
-    SR_HIP_CHECK(sr_launch_eval_param<T>(fa, fr.p, SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, int(fr.n_blocks), cs));
-  else
-    SR_HIP_CHECK(sr_launch_eval<T>(fa, SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, int(fr.n_blocks), cs));
+  // the FOLD build of the region's loss launch (a candidate launch's: the plain register-stack FOLD build)
+  const SrBuildRequest q{int(sizeof(T)), SR_MODE_FOLD, job.gather, job.tier, fr.Rc, fr.g.W, fr.vstk, fa.loss_kind,
+                         fa.ptab ? SR_FAMILY_PARAM : SR_FAMILY_PLAIN};
+  SR_HIP_CHECK(sr_launch_eval<T>(fa, q, int(fr.n_blocks), cs));
   return SR_OK;
 }
 // A region's walk: the folds' values and status at the caller's tree index (out arrays and carry are
@@ -714,9 +713,11 @@ struct BatchCall {
   int nfk = 0;
   int64_t p_stride = 0;
   double max_abs_p = 0.0;
-  // choose_kernels: tier, rows per lane (classic R, register-stack Rv or 0), waves; every grid's spec;
-  // row blocks the partial buffers hold per tree (the most any kernel uses); the chunks
+  // choose_kernels: tier, rows per lane (classic R, register-stack Rv or 0), waves; the build request of the
+  // call's launches (each launch sets its own R, waves, stack and view); every grid's spec; row blocks the
+  // partial buffers hold per tree (the most any kernel uses); the chunks
   int tier = 0, R = 0, W = 0, Rv = 0, n_rb = 1, n_chunks = 1;
+  SrBuildRequest breq;
   GridSpec gs;
   Grid g_ls, g_vs;  // the whole batch's grids at R (depth 1) and, Rv > 0, at Rv (depth 0)
   Grid glast;       // the last launch's (BatchResult::grid)
@@ -843,21 +844,17 @@ struct BatchCall {
       if (!(mx < double(tbig()) / double(lmax))) tier = SR_TIER_FULL;
     }
 #endif
-    // (a parametric call's kernels are a smaller set, sr_launch_eval_param: the classic kernel at its
-    //  default rows per lane, 4 waves, one register-stack build per type; its knobs map onto that set)
-    // (an expression-loss call's likewise, sr_launch_eval_lossx: the classic kernel at its default rows per
-    //  lane, 4 waves, no register-stack build — the "rows_per_lane" / "waves" / register-stack knobs map onto it)
-    const bool small_set = parametric || lexpr != nullptr;
-    R = sr_rows_per_lane<T>(want.mode, tier, small_set ? 0 : ctx->rows_override);
-    W = small_set ? 4 : sr_waves_per_block(int(sizeof(T)), want.mode, tier, R, ctx->waves_override);
     // register-stack kernel (f32 BASIC loss over the full dataset): Rv rows per lane, used for every
     // chunk whose programs need <= 2 operand-stack slots (all trees of <= 30 nodes); other chunks run
     // the LDS-stack kernel at R rows per lane
-    Rv = (want.mode == SR_MODE_LOSS && tier == SR_TIER_BASIC && !gather)
-               ? sr_vstk_rows(int(sizeof(T)), n_eval, ctx->vstk_rows ? ctx->vstk_rows : ctx->rows_override)
-               : 0;
-    if (parametric && Rv > 0) Rv = sizeof(T) == 4 ? 16 : 8;  // (the one register-stack build of a parametric call)
-    if (lexpr) Rv = 0;
+    const SrBuildFamily family = parametric ? SR_FAMILY_PARAM : (lexpr ? SR_FAMILY_LOSSX : SR_FAMILY_PLAIN);
+    const SrLaunchShape shape = sr_launch_shape(int(sizeof(T)), want.mode, tier, gather, family, n_eval, ctx->rows_override,
+                                                ctx->waves_override, ctx->vstk_rows);
+    R = shape.R;
+    W = shape.W;
+    Rv = shape.Rv;
+    // (an expression-loss call's launches are plain ones whose loss kind is SR_LOSS_EXPR: sr_resolve_build)
+    breq = SrBuildRequest{int(sizeof(T)), want.mode, gather, tier, R, W, false, lkind, parametric ? SR_FAMILY_PARAM : SR_FAMILY_PLAIN};
     // every grid of the call comes from this one spec
     gs = GridSpec{int(sizeof(T)), n_eval, W, nfk, req.ds->w != nullptr, ctx->tree_group, mrb};
     // a wide dataset whose register-stack tile (its rows per lane are twice the classic kernel's) would
@@ -1301,8 +1298,7 @@ struct BatchCall {
   // The argument blocks of one launch over launch positions [p0, p0 + np) of the chunk; its partials
   // occupy [n_rb][np] words from p0 * n_rb (the chunk's region holds n_rb rows for every position).
   // out_sum (the reduce's routing), segs and fold_cand are the launch's own (launch_region).
-  void fill_region_args(const BatchChunk<T>& ch, int64_t p0, int64_t np, bool vstk, const Grid& g,
-                        SrEvalArgs<T>* out, SrParamArgs<T>* pout) {
+  void fill_region_args(const BatchChunk<T>& ch, int64_t p0, int64_t np, bool vstk, const Grid& g, SrEvalArgs<T>* out) {
     const int64_t t0 = ch.t0;
     const int Rc = vstk ? Rv : R;
     SrEvalArgs<T>& a = *out = SrEvalArgs<T>{};
@@ -1323,11 +1319,10 @@ struct BatchCall {
     a.dld = dld;
     a.n_rows = n_eval;
     a.nf = nfk;
-    SrParamArgs<T>& pa_ = *pout = SrParamArgs<T>{};
     if (parametric) {  // (the chunk's rows of the table: the kernel indexes it by the chunk-local tree index)
-      pa_.ptab = ctx->ptab.as<T>() + size_t(t0) * size_t(p_stride);
-      pa_.p_stride = int(p_stride);
-      pa_.n_classes = int(pb->n_classes);
+      a.ptab = ctx->ptab.as<T>() + size_t(t0) * size_t(p_stride);
+      a.p_stride = int(p_stride);
+      a.n_classes = int(pb->n_classes);
     }
     a.tiles_per_block = g.tiles;
     a.n_row_blocks = g.n_row_blocks;
@@ -1392,8 +1387,7 @@ struct BatchCall {
   // a wide, short grid: 16 trees x 1 tile per workgroup, kProbeTiles row blocks; always the
   // classic kernel at R rows per lane (a register-stack launch's 2x longer tiles would double the
   // probe's work for the same verdicts: C2's dead trees 0.88 -> 0.6x ms)
-  int launch_probe(const BatchChunk<T>& ch, const SrEvalArgs<T>& a, const SrParamArgs<T>& pa_,
-                   int64_t np, const Grid& g) {
+  int launch_probe(const BatchChunk<T>& ch, const SrEvalArgs<T>& a, int64_t np, const Grid& g) {
     SrEvalArgs<T> pa = a;
     pa.fold_loss = nullptr;  // (its rows are the stress rows; the main launch stores the view's)
     pa.stack_depth = ch.depth;
@@ -1416,12 +1410,9 @@ struct BatchCall {
         pa.dld = kProbeRows;
       }
     }
-    if (parametric)
-      SR_HIP_CHECK(sr_launch_eval_param<T>(pa, pa_, want.mode, gather || stress_probe, tier, R, W, false,
-                                           pa.n_groups * kProbeTiles, ch.cs));
-    else
-      SR_HIP_CHECK(sr_launch_eval<T>(pa, want.mode, gather || stress_probe, tier, R, W, false, pa.n_groups * kProbeTiles,
-                                     ch.cs));
+    SrBuildRequest q = breq;  // (the classic kernel at the call's R and W)
+    q.gather = gather || stress_probe;
+    SR_HIP_CHECK(sr_launch_eval<T>(pa, q, pa.n_groups * kProbeTiles, ch.cs));
     return SR_OK;
   }
 
@@ -1439,8 +1430,7 @@ struct BatchCall {
     if (g.n_blocks > 0x7fffffff || g.n_row_blocks > n_rb) return set_error(SR_ERR_INVALID_ARG, "grid too large");
     glast = g;
     SrEvalArgs<T> a;
-    SrParamArgs<T> pa_;
-    fill_region_args(ch, p0, np, vstk, g, &a, &pa_);
+    fill_region_args(ch, p0, np, vstk, g, &a);
     int64_t n_blocks = g.n_blocks;
     if (multi) {  // (one launch over the whole chunk: the segments order_and_stage computed)
       a.segs = reinterpret_cast<const SrSegment*>(dprog + img.o_seg);
@@ -1462,7 +1452,7 @@ struct BatchCall {
     //  216.9 -> 214.4 ms per call, C2 unchanged; tools/c4_shard_probe.py, profiles/r05_ab_c4_shard.txt)
     const bool probe_first = ch.nc >= 512 && n_eval >= (int64_t(1) << 18);
     const bool probed = use_probe && p0 == 0 && g.n_row_blocks >= 16 && (ctx->probe != 2 || ch.c > 0 || probe_first);
-    if (probed) SR_STAGE(launch_probe(ch, a, pa_, np, g));
+    if (probed) SR_STAGE(launch_probe(ch, a, np, g));
 #ifdef SR_STAMPS
     ctx->n_stamps = g.n_blocks * g.W * SR_NSTAMPS;
     SR_HIP_CHECK(ctx->stamps.ensure(size_t(ctx->n_stamps) * sizeof(uint64_t)));
@@ -1498,13 +1488,13 @@ struct BatchCall {
       last.loss_listed_np[ch.c] = np;
       last.loss_list_read = false;
     }
-    if (parametric)
-      SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, want.mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
-    else if (cand_launch)
-      SR_HIP_CHECK(sr_launch_loss_cand<T>(a, Rc, g.W, int(n_blocks), cs));
-    else
-      SR_HIP_CHECK(sr_launch_eval<T>(a, want.mode, gather, tier, Rc, g.W, vstk, int(n_blocks), cs));
-    if (fold.path) fjob.regions.push_back({a, pa_, t0, t0 + p0, np, n_blocks, Rc, vstk, g, fold_compact ? sr_fold_region(ch.c, vstk) : -1});
+    SrBuildRequest q = breq;
+    q.R = Rc;
+    q.waves = g.W;
+    q.vstk = vstk;
+    if (cand_launch) q.family = SR_FAMILY_CAND;  // (never a parametric call's: fold_cand)
+    SR_HIP_CHECK(sr_launch_eval<T>(a, q, int(n_blocks), cs));
+    if (fold.path) fjob.regions.push_back({a, t0, t0 + p0, np, n_blocks, Rc, vstk, g, fold_compact ? sr_fold_region(ch.c, vstk) : -1});
     if (!direct && host_red)
       ctx->host_reductions.push_back({t0 + p0, np, g.n_row_blocks});
     else if (listed)
@@ -1924,11 +1914,10 @@ int run_exact(sr_ctx* ctx, const EvalReq& req, const SrProgramBatch<T>& prog, co
     a.ld = ds->ld;
     a.n_rows = n_eval;
     a.nf = nfk;
-    SrParamArgs<T> pa_{};
     if (pb) {
-      pa_.ptab = ctx->ptab.as<T>();
-      pa_.p_stride = int(pb->max_parameters) * int(pb->n_classes);
-      pa_.n_classes = int(pb->n_classes);
+      a.ptab = ctx->ptab.as<T>();
+      a.p_stride = int(pb->max_parameters) * int(pb->n_classes);
+      a.n_classes = int(pb->n_classes);
     }
     a.tiles_per_block = int((max_len + rows - 1) / rows);
     a.n_row_blocks = int(n_ranges);
@@ -1942,10 +1931,9 @@ int run_exact(sr_ctx* ctx, const EvalReq& req, const SrProgramBatch<T>& prog, co
     const int64_t blocks = int64_t(a.n_groups) * n_ranges;
     if (blocks > 0x7fffffff) return set_error(SR_ERR_INVALID_ARG, "grid too large");
     SR_HIP_CHECK(hipEventRecord(ctx->ev_k0, s));
-    if (pb)
-      SR_HIP_CHECK(sr_launch_eval_param<T>(a, pa_, SR_MODE_EXACT, gather, etier, R, W, false, int(blocks), s));
-    else
-      SR_HIP_CHECK(sr_launch_eval<T>(a, SR_MODE_EXACT, gather, etier, R, W, false, int(blocks), s));
+    const SrBuildRequest q{int(sizeof(T)), SR_MODE_EXACT, gather, etier, R, W, false, a.loss_kind,
+                           pb ? SR_FAMILY_PARAM : SR_FAMILY_PLAIN};
+    SR_HIP_CHECK(sr_launch_eval<T>(a, q, int(blocks), s));
     if (host_finite) {
       const int64_t n_arrays = nb * max_checks;
       SR_HIP_CHECK(ctx->jsum_scratch.ensure(size_t(std::max<int64_t>(1, n_arrays * n_internal)) * sizeof(T)));

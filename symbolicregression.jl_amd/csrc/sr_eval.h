@@ -5,6 +5,7 @@
 #include "sr_ops.h"
 #include "sr_loss_expr.h"  // the expression-loss program and its interpreters (HIP-free)
 #include "sr_plan.h"  // modes, tiers, SrSegment, SrDerivedSpec, the launch-shape functions (HIP-free)
+#include "sr_builds.h"  // the builds of sr_tile_kernel, SrBuildRequest and the rule that resolves one (HIP-free)
 #include "../../include/sr_amd.h"
 
 // The deferred checks leave bounded outputs untracked (sr_tile_impl.h sr_untracked_u / _b; round 5:
@@ -136,8 +137,9 @@ struct SrEvalArgs {
   // -DSR_STAMPS builds only (latency analysis, tools/stamps.py): per wave, SR_NSTAMPS wall-clock
   // stamps at fixed points of the kernel, [block][wave][SR_NSTAMPS]; NULL otherwise
   uint64_t* stamps;
-  // the builds for parametric calls (SR_TIER_PARAM, sr_inst_*param*.hip; no other kernel reads these,
-  // sr_launch_tile_param fills them from SrParamArgs)
+  // the builds for parametric calls (SR_TIER_PARAM; no other kernel reads these): the call's table,
+  // ptab[tree * p_stride + k * n_classes + class] at the caller's tree index (as `offsets`).  The rows' 0-based
+  // classes are the last staged X row (the dataset's hidden row: nf counts it).
   const T* ptab;
   int p_stride;
   int n_classes;
@@ -166,53 +168,22 @@ struct SrEvalArgs {
   double* fold_est_sum;
   uint32_t* fold_est_cnt;
   uint32_t fold_est_min;
-  // SR_LOSS_EXPR loss builds (sr_inst_*lossx*.hip; last again, no other kernel reads them): the loss
+  // SR_LOSS_EXPR loss builds (last again, no other kernel reads them): the loss
   // program (sr_loss_expr.h) in a device buffer of the context — not in the argument block, which is host
   // memory here — read with wave-uniform loads, and its length
   const SrIns<T>* lx_code;
   int lx_n;
 };
-// A parametric call's table: ptab[tree * p_stride + k * n_classes + class] at the caller's tree index (as
-// `offsets`).  The rows' 0-based classes are the last staged X row (the dataset's hidden row:
-// SrEvalArgs::nf counts it).
-template <typename T>
-struct SrParamArgs {
-  const T* ptab;
-  int p_stride;
-  int n_classes;
-};
 constexpr int SR_NSTAMPS = 8;
 
 template <typename T, int R, int MODE, bool GATHER, int TIER, int W = 4, int LK = -1, bool VSTK = false>
 hipError_t sr_launch_tile(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s);
-template <typename T, int R, int MODE, bool GATHER, int TIER, int W = 4, int LK = -1, bool VSTK = false>
-hipError_t sr_launch_tile_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int n_blocks, hipStream_t s);
-// Runtime dispatch over the instantiated kernels: R rows per lane (sr_rows_per_lane, or
-// sr_vstk_rows with vstk = true: operand stack in VGPRs, programs of <= 2 stack slots).
+// The one launcher of the tile kernels: resolves the request (sr_builds.h: sr_resolve_build) and launches
+// the build it names; hipErrorInvalidValue for a refused request, a build that is not in the table, a
+// request whose element size or loss kind is not the arguments', and arguments the build needs but lacks
+// (SR_TIER_CAND: fold_cand; SR_LOSS_EXPR: the loss program; SR_TIER_PARAM: the table, in sr_launch_tile).
 template <typename T>
-hipError_t sr_launch_eval(const SrEvalArgs<T>& a, int mode, bool gather, int tier, int R, int waves, bool vstk,
-                          int n_blocks, hipStream_t s);
-// The candidate-composing loss launch of a large plain call under the in-order fold (SR_TIER_CAND:
-// Float32, BASIC tier, full view, register stack at 16 rows per lane, 4 waves; a.fold_cand set);
-// hipErrorInvalidValue for any other shape.
-template <typename T>
-hipError_t sr_launch_loss_cand(const SrEvalArgs<T>& a, int R, int waves, int n_blocks, hipStream_t s);
-// The same over the kernels built for parametric calls (LOAD_PARAM / P operands; sr_inst_*param*.hip), a
-// smaller set: Float32 BASIC loss at 8 rows per lane (classic, full view or gathered) and 16 (register
-// stack), Float64 at 4 and 8, the FULL tier at 4 / 2, PRED, EXACT with 4 waves (FULL-tier build) and the
-// Float32 FOLD builds of those loss launches; hipErrorInvalidValue for any other shape (the host maps a
-// parametric call's knobs onto this set: sr_capi.cpp choose_kernels).
-template <typename T>
-hipError_t sr_launch_eval_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int mode, bool gather, int tier, int R,
-                                int waves, bool vstk, int n_blocks, hipStream_t s);
-// The loss launches of an expression-loss call (a.loss_kind == SR_LOSS_EXPR; sr_inst_*lossx*.hip): the
-// classic kernel at its default rows per lane — Float32 BASIC 8 / FULL 4, Float64 4 / 2 — full view or
-// gathered, 4 waves; hipErrorInvalidValue for any other shape or a missing program (the host maps such a
-// call's knobs onto this set: sr_capi.cpp choose_kernels).  sr_launch_eval routes LOSS launches of such
-// arguments here itself: no generic-loss kernel, whose default case is L2, ever runs them.
-template <typename T>
-hipError_t sr_launch_eval_lossx(const SrEvalArgs<T>& a, bool gather, int tier, int R, int waves, bool vstk, int n_blocks,
-                                hipStream_t s);
+hipError_t sr_launch_eval(const SrEvalArgs<T>& a, const SrBuildRequest& req, int n_blocks, hipStream_t s);
 template <typename T>
 hipError_t sr_launch_derived(const T* X, int64_t ld, const int64_t* row_idx, int64_t n_view, int64_t n_pad,
                              const SrDerivedSpec& spec, T* out, int64_t dld, hipStream_t s);
@@ -321,7 +292,7 @@ hipError_t sr_launch_grad_reduce(const double* part, int n_row_blocks, int n_val
 // + class; SrGradArgs::nf counts the staged hidden class row.
 template <typename T>
 struct SrGradParamArgs {
-  const T* ptab;              // [tree][parameter][class], as SrParamArgs
+  const T* ptab;              // [tree][parameter][class], as SrEvalArgs::ptab
   int p_stride;
   int n_classes;
   const uint32_t* tan_off;    // [n_trees + 1]
@@ -361,7 +332,7 @@ inline int sr_grad_param_launch_rows(int elem_size, int kt, int nf, bool weighte
 template <typename T, bool GATHER>
 hipError_t sr_launch_grad_param_any(const SrGradArgs<T>& a, const SrGradParamArgs<T>& p, int kt, int rows, int n_blocks,
                                     hipStream_t s);
-// The expression-loss build of the gradient kernel (sr_grad_lossx_kernel, sr_grad_lossx_*.hip): d loss / d
+// The expression-loss build of the gradient kernel (sr_grad_lossx_kernel, sr_grad_inst.hip): d loss / d
 // pred from the loss program, the weight handed to it.  One build per tangent width, at sr_grad_param_rows
 // rows per lane (the plain kernel's preferred count); hipErrorInvalidValue for any other.
 template <typename T, bool GATHER>

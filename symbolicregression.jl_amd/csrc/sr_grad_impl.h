@@ -120,7 +120,7 @@ constexpr uint32_t SR_GV_PL = 100u, SR_GV_PR = 101u;
 // reduced in order (sr_launch_grad_reduce).  No atomics: the same bits run to run, for every R and
 // whatever else is in the launch.
 //
-// LOSSX (sr_grad_lossx_kernel, expression losses; sr_grad_lossx_*.hip): only the per-row coefficient differs —
+// LOSSX (sr_grad_lossx_kernel, expression losses; sr_grad_inst.hip): only the per-row coefficient differs —
 // d value / d pred from the call's loss program by forward mode (sr_loss_expr.h), the weight handed to the
 // program and not multiplied in afterwards.
 template <typename T, int KT, int W, bool GATHER, int R>
@@ -171,7 +171,7 @@ hipError_t sr_launch_grad_rows_from(const SrGradArgs<T>& a, int rows, int n_bloc
 }
 
 // The parametric builds: rows per lane sr_grad_param_rows(sizeof(T), KT) and 1 (sr_grad_param_launch_rows
-// picks one), one translation unit per element type and gather mode (sr_grad_param_*.hip).
+// picks one), one translation unit per element type and gather mode (sr_grad_inst.hip).
 template <typename T, int KT, int W, bool GATHER, int R>
 hipError_t sr_launch_grad_param(const SrGradArgs<T>& a, const SrGradParamArgs<T>& p, int n_blocks, hipStream_t s) {
   if (p.ptab == nullptr || p.n_classes < 1 || a.nf < 2) return hipErrorInvalidValue;

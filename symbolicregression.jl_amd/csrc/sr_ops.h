@@ -103,7 +103,7 @@ SR_HD inline bool sr_loss_propagates_nan(int32_t kind) {
 //                             (k in the operand index): a gather from the call's per-tree parameter table by
 //                             the row's class, which the dataset keeps as one hidden extra row of X.  In every
 //                             other respect a feature leaf (checked like one, never folded); only the kernels
-//                             built for parametric calls (sr_inst_*param*.hip) implement it
+//                             built for parametric calls (SR_TIER_PARAM, sr_builds.h) implement it
 //       SR_OP_PBIN0 + 2*(b-1) + {SR_V_PL, SR_V_PR}   tos <- op_b(P[k], tos) / op_b(tos, P[k]): the parameter
 //                             leaf as a binary node's operand, as the F variants take a feature (+ and *: PR only)
 //       SR_OP_LOAD_DERIVED (_PUSH)  tos <- D[k]: a derived column op_u(X[f]) computed once per call

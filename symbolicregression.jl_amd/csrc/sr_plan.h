@@ -46,7 +46,7 @@ struct SrDerivedSpec {
 };
 
 // ---------------------------------------------------------------- launch shapes of the tile kernels
-// Rows per lane of each instantiated kernel (sr_inst_*.hip): f32 BASIC 8 (4 for tuning), f32 FULL 4,
+// Rows per lane of each instantiated kernel (sr_builds.h): f32 BASIC 8 (4 for tuning), f32 FULL 4,
 // f64 BASIC 4, f64 FULL 2.  `rows_per_lane` <= 0 picks the default.
 template <typename T>
 inline int sr_rows_per_lane(int mode, int tier, int requested) {

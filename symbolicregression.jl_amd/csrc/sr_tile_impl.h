@@ -1707,6 +1707,9 @@ __global__ void __launch_bounds__(W * 64, (SrMinWavesKernel<T, R, (TIERP & SR_TI
 template <typename T, int R, int MODE, bool GATHER, int TIER, int W, int LK, bool VSTK>
 hipError_t sr_launch_tile(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s) {
   if (VSTK && a.stack_depth > SR_VSTK_SLOTS) return hipErrorInvalidValue;  // host routes deeper programs elsewhere
+  if constexpr ((TIER & SR_TIER_PARAM) != 0) {  // a parametric call's table (a.nf counts the hidden class row: >= 2 staged rows)
+    if (a.ptab == nullptr || a.n_classes < 1 || a.p_stride < 0 || a.nf < 2) return hipErrorInvalidValue;
+  }
   const SrLdsPlan<T> plan(a.nf, 64 * R, VSTK ? 0 : a.stack_depth, a.trees_per_block,
                           MODE == SR_MODE_EXACT ? a.max_checks : 0, W, a.w != nullptr,
                           (MODE == SR_MODE_LOSS || MODE == SR_MODE_FOLD) ? a.code_lds : 0);
@@ -1717,17 +1720,6 @@ hipError_t sr_launch_tile(const SrEvalArgs<T>& a, int n_blocks, hipStream_t s) {
   }
   hipLaunchKernelGGL((sr_tile_kernel<T, R, MODE, GATHER, TIER, W, LK, VSTK>), dim3(n_blocks), dim3(W * 64), plan.total, s, a);
   return hipGetLastError();
-}
-// the same for a parametric call: the build flagged SR_TIER_PARAM, the table in the argument block's last
-// fields (a.nf counts the hidden class row: at least 2 staged rows)
-template <typename T, int R, int MODE, bool GATHER, int TIER, int W, int LK, bool VSTK>
-hipError_t sr_launch_tile_param(const SrEvalArgs<T>& a, const SrParamArgs<T>& p, int n_blocks, hipStream_t s) {
-  if (p.ptab == nullptr || p.n_classes < 1 || p.p_stride < 0 || a.nf < 2) return hipErrorInvalidValue;
-  SrEvalArgs<T> b = a;
-  b.ptab = p.ptab;
-  b.p_stride = p.p_stride;
-  b.n_classes = p.n_classes;
-  return sr_launch_tile<T, R, MODE, GATHER, TIER | SR_TIER_PARAM, W, LK, VSTK>(b, n_blocks, s);
 }
 
 // ------------------------------------------------------------------ derived columns
@@ -1773,28 +1765,3 @@ hipError_t sr_launch_derived(const T* X, int64_t ld, const int64_t* row_idx, int
   hipLaunchKernelGGL((sr_derived_kernel<T, R>), grid, dim3(256), 0, s, X, ld, row_idx, n_view, n_pad, spec, out, dld);
   return hipGetLastError();
 }
-#define SR_INSTANTIATE_DERIVED(T)                                                                            \
-  template hipError_t sr_launch_derived<T>(const T*, int64_t, const int64_t*, int64_t, int64_t, const SrDerivedSpec&, \
-                                           T*, int64_t, hipStream_t);
-
-// Explicit instantiations are spread over several translation units (sr_inst_*.hip, one per
-// element type / mode) so the build compiles them in parallel; see the Makefile.
-#define SR_INSTANTIATE_WLV(T, R, MODE, GATHER, TIER, W, LK, VSTK) \
-  template hipError_t sr_launch_tile<T, R, MODE, GATHER, TIER, W, LK, VSTK>(const SrEvalArgs<T>&, int, hipStream_t);
-// the builds for parametric calls (sr_inst_*param*.hip; the set sr_launch_eval_param dispatches over)
-#define SR_INSTANTIATE_PARAM(T, R, MODE, GATHER, TIER, W, LK, VSTK) \
-  template hipError_t sr_launch_tile_param<T, R, MODE, GATHER, TIER, W, LK, VSTK>(const SrEvalArgs<T>&, const SrParamArgs<T>&, int, \
-                                                                                  hipStream_t);
-#define SR_INSTANTIATE_WL(T, R, MODE, GATHER, TIER, W, LK) SR_INSTANTIATE_WLV(T, R, MODE, GATHER, TIER, W, LK, false)
-#define SR_INSTANTIATE_W(T, R, MODE, GATHER, TIER, W) SR_INSTANTIATE_WL(T, R, MODE, GATHER, TIER, W, -1)
-#define SR_INSTANTIATE(T, R, MODE, GATHER, TIER) SR_INSTANTIATE_WL(T, R, MODE, GATHER, TIER, 4, -1)
-// BASIC-tier loss kernels: one instantiation per elementwise loss
-#define SR_INSTANTIATE_LOSS(T, R, GATHER)                                   \
-  SR_INSTANTIATE_WL(T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, SR_LOSS_L2) \
-  SR_INSTANTIATE_WL(T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, SR_LOSS_L1) \
-  SR_INSTANTIATE_WL(T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, -1)
-// register-stack BASIC-tier loss kernels (f32, 16 / 32 rows per lane)
-#define SR_INSTANTIATE_LOSS_VSTK(T, R, GATHER)                                     \
-  SR_INSTANTIATE_WLV(T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, SR_LOSS_L2, true) \
-  SR_INSTANTIATE_WLV(T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, SR_LOSS_L1, true) \
-  SR_INSTANTIATE_WLV(T, R, SR_MODE_LOSS, GATHER, SR_TIER_BASIC, 4, -1, true)

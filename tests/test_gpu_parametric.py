@@ -1,4 +1,4 @@
-"""GPU: ParametricExpression trees scored on the device (LOAD_PARAM / P operands, sr_inst_*param*.hip).
+"""GPU: ParametricExpression trees scored on the device (LOAD_PARAM / P operands, the SR_TIER_PARAM builds of csrc/sr_builds.h).
 
 A parameter leaf p_k reads parameters[k, class[row]] of its own tree's matrix; DynamicExpressions evaluates
 it as feature leaf nfeatures + k of vstack(X, parameters[:, class]).  So every parametric result has a

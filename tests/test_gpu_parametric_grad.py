@@ -1,5 +1,5 @@
 """GPU: gradients and constant optimisation of ParametricExpression trees (sr_eval_grad_batch_parametric,
-sr_eval_grad_batch_views_parametric, sr_optimize_constants_batch_parametric; sr_grad_param_*.hip).
+sr_eval_grad_batch_views_parametric, sr_optimize_constants_batch_parametric; sr_grad_inst.hip).
 
 Tree t's gradient is [its constants in pre-order | K x C parameter entries, column-major] (DynamicExpressions'
 get_scalar_constants order).  A parametric tree's plain twin is the same tree with p_k as feature nf + k on
