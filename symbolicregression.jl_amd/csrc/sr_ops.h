@@ -295,7 +295,8 @@ SR_HD inline T sr_unary(uint32_t op, T x) {
     case SR_U_LOG: return x > T(0) ? M::log(x) : sr_qnan<T>();        // safe_log  :50-52
     case SR_U_LOG2: return x > T(0) ? M::log2(x) : sr_qnan<T>();      // safe_log2 :53-55
     case SR_U_LOG10: return x > T(0) ? M::log10(x) : sr_qnan<T>();    // safe_log10 :56-58
-    case SR_U_LOG1P: return x > T(-1) ? M::log1p(x) : sr_qnan<T>();   // safe_log1p :59-61
+    // (x == 0 returns x: OCML's Float64 log1p and both its expm1 return +0.0 at -0.0, Julia's -0.0, as the host's)
+    case SR_U_LOG1P: return x > T(-1) ? (x == T(0) ? x : M::log1p(x)) : sr_qnan<T>();   // safe_log1p :59-61
     case SR_U_SQRT: return x >= T(0) ? M::sqrt(x) : sr_qnan<T>();     // safe_sqrt :74-76
     case SR_U_ABS: return x < T(0) ? -x : (x == T(0) ? T(0) : x);
     case SR_U_SIGN: return x < T(0) ? T(-1) : (x > T(0) ? T(1) : x);  // Julia sign (NaN -> NaN)
@@ -317,7 +318,7 @@ SR_HD inline T sr_unary(uint32_t op, T x) {
     case SR_U_FLOOR: return M::floor(x);
     case SR_U_CEIL: return M::ceil(x);
     case SR_U_EXP2: return M::exp2(x);
-    case SR_U_EXPM1: return M::expm1(x);
+    case SR_U_EXPM1: return x == T(0) ? x : M::expm1(x);
     default: return sr_qnan<T>();
   }
 }

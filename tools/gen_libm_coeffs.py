@@ -73,6 +73,7 @@ def tables():
         return mp.mpf(struct.unpack("<f", struct.pack("<I", bits))[0])
 
     trig = [(float(mp.sin(k * mp.pi / 64)), float(mp.cos(k * mp.pi / 64))) for k in range(128)]
+    trig[0] = (-0.0, trig[0][1])  # s_0 = -0.0: sin(-0.0) = -0.0 and sin(+0.0) = +0.0 (sr_libm_tables.h)
     logt, rmax = [], mp.mpf(0)
     for i in range(64):
         lo, hi = f32(LOG_OFF + (i << 17)), f32(LOG_OFF + ((i + 1) << 17))
