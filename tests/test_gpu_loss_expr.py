@@ -4,6 +4,12 @@ sr_register_loss_expr) through scoring, gradients, constant opti
 An expression-loss call returns the f64 sum of the element values divided once, so the oracle comparisons
 use the oracle's f64 accumulation (loss_expr_util.loss_tolerance_f64).  Every test here fails where
 ``Options`` refuses the string.
+
+Every test here reads a mean over thousands of rows of random trees.  The per-element suites are
+test_gpu_loss_expr_forms.py (every instruction form, DX / DY flag and live-value depth of the loss program, bit
+for bit per element on all eight tile builds; the tangent widths), test_gpu_loss_expr_ops.py (every operator of the
+catalog inside a loss program, per value) and test_gpu_loss_expr_rules.py (every derivative rule through a loss
+program against mpmath); their CPU halves are test_loss_expr_forms_host.py and test_loss_expr_rules_host.py.
 """
 import ctypes
 
