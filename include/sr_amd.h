@@ -211,6 +211,31 @@ int sr_eval_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr
                        const int64_t* row_idx, int64_t n_idx, void* out_pred, uint8_t* out_complete);
 
 /*
+ * Batched eval_grad_tree_array / eval_diff_tree_array (src/InterfaceDynamicExpressions.jl:153-165, 118-130):
+ * the predictions and, per ROW, their derivatives (plain trees; dataset dtype).
+ *
+ * out_pred[n_trees][n_rows] and the value part of out_complete are sr_eval_tree_array's for the same
+ * arguments, bit for bit.  sr_eval_grad_tree_array: tree t has n_grad_t derivative arrays — variable = 0:
+ * one per constant, in pre-order (get_scalar_constants, sr_eval_grad_batch's order); variable != 0: one per
+ * feature 1..nfeatures (exactly 0 for a feature the tree does not use).  out_grad holds, per tree,
+ * [n_grad_t][n_rows] with rows fastest; tree t's block starts at the running sum of n_grad_u * n_rows over
+ * the trees u < t.  sr_eval_diff_tree_array: out_diff[n_trees][n_rows], tree t's derivative with respect to
+ * feature direction[t] (1-based) — row direction[t] - 1 of the variable != 0 result, bit for bit.
+ * Derivatives are forward mode in the dataset's type with sr_eval_grad_batch's rules (csrc/sr_ops.h).
+ * out_complete[t] is sr_eval_tree_array's flag AND no returned derivative element of tree t is NaN or +-Inf;
+ * an incomplete tree's derivatives are all 0.
+ * SR_ERR_UNSUPPORTED_OP for an operator set with an operator that has no derivative rule (gamma),
+ * SR_ERR_TOO_DEEP for more than 128 constants in a tree, SR_ERR_INVALID_ARG for a direction outside
+ * 1..nfeatures and for a feature count whose staged tile does not fit the kernel's LDS at one row per lane.
+ */
+int sr_eval_grad_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                            const int64_t* row_idx, int64_t n_idx, int variable, void* out_pred, void* out_grad,
+                            uint8_t* out_complete);
+int sr_eval_diff_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                            const int64_t* row_idx, int64_t n_idx, const int32_t* direction /* per tree, 1-based */,
+                            void* out_pred, void* out_diff /* [n_trees][n_rows] */, uint8_t* out_complete);
+
+/*
  * The three calls above for ParametricExpression trees (eval_tree_dispatch(::ParametricExpression, ...),
  * src/ParametricExpression.jl:69-100): the plain call's arguments plus the batch's parameter side, the
  * same outputs.  `ds` must come from sr_dataset_upload_classes with params->n_classes classes
@@ -630,7 +655,8 @@ int sr_last_phase_ms(sr_ctx* ctx, double* out, int n);
  * reports how many derived columns the last sr_eval_loss_batch used and how many of its trees went
  * through the exact-sum pass (flagged BIG). */
 int sr_set_tuning(sr_ctx* ctx, const char* name, int64_t value);
-/* The last sr_eval_grad_batch(_views) call's tangent kernels, per tangent bucket b = 0..4 (1, 2, 4, 8,
+/* The last sr_eval_grad_batch(_views) / sr_eval_grad_tree_array / sr_eval_diff_tree_array call's tangent kernels
+ * (the per-row calls: summed over the call's chunks, no loss epilogue in the flops), per tangent bucket b = 0..4 (1, 2, 4, 8,
  * 16 tangents; up to n of each output, each may be NULL): device time (ms, HIP events; 0 when the
  * context's "timing" is off or the bucket was empty), algorithmic flops (per row of a (tree, first
  * tangent) work item: each unary node 2 + KT, each binary node 3 + 2 KT, the loss epilogue 3 + KT),

@@ -173,6 +173,7 @@ struct sr_ctx : SrKnobs {
   hipEvent_t ev_f[5] = {};
   double fold_ms[4] = {0, 0, 0, 0};
   bool grad_timed[kGradBuckets] = {};
+  double grad_ms_done[kGradBuckets] = {};  // (a chunked call's earlier launches of the bucket, read back already)
   double grad_flops[kGradBuckets] = {};
   int64_t grad_items[kGradBuckets] = {};
   int grad_rows[kGradBuckets] = {};
@@ -2995,6 +2996,7 @@ int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_gr
   static_assert(kNB == sr_ctx::kGradBuckets, "gradient buckets");
   for (int b = 0; b < kNB; ++b) {
     ctx->grad_timed[b] = false;
+    ctx->grad_ms_done[b] = 0.0;
     ctx->grad_items[b] = int64_t(items[b].size());
     ctx->grad_rows[b] = lc[b].rows;
     double per_row = 0.0;
@@ -3094,6 +3096,273 @@ int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_gr
       }
     }
   }
+  return SR_OK;
+}
+
+// Per-row derivatives (sr_eval_grad_tree_array / sr_eval_diff_tree_array): the predictions and
+// their flags from the PRED path (eval_pred_impl: sr_eval_tree_array's, bit for bit), then every complete
+// tree's tangents from the per-row build of the gradient kernel.  mode: the constants' tangents, the
+// features', or one feature's per tree (direction, 1-based).
+enum RowGradMode { kRowGradConsts = 0, kRowGradFeatures = 1, kRowGradDiff = 2 };
+// (device staging of the tangents: work items (tree, window) are launched in chunks whose outputs stay within
+// the "grad_stage_bytes" knob, 256 MiB — one item's own output when that is larger; results do not depend on it)
+
+template <typename T>
+int eval_row_grad_impl(sr_ctx* ctx, const EvalReq& req, int mode, const int32_t* direction, void* out_pred, void* out_grad,
+                       uint8_t* out_complete) {
+  const sr_dataset* const ds = req.ds;
+  const sr_tree_batch* const trees = req.trees;
+  const SrOpset& ops = ctx->opsets[req.opset_id];
+  for (uint32_t u : ops.unary)
+    if (!sr_unary_grad_supported(u)) return set_error(SR_ERR_UNSUPPORTED_OP, "operator without a gradient rule");
+  for (uint32_t b : ops.binary)
+    if (!sr_binary_grad_supported(b)) return set_error(SR_ERR_UNSUPPORTED_OP, "operator without a gradient rule");
+  const int64_t nt = trees->n_trees;
+  const int64_t n_eval = req.n_eval();
+  const bool gather = req.gather();
+  const bool feat = mode != kRowGradConsts;
+  constexpr int kNB = sr_ctx::kGradBuckets;
+  constexpr int kWaves = 4;
+  const int kts[kNB] = {1, 2, 4, 8, 16};
+  for (int b = 0; b < kNB; ++b) {
+    ctx->grad_timed[b] = false;
+    ctx->grad_ms_done[b] = 0.0;
+    ctx->grad_flops[b] = 0.0;
+    ctx->grad_items[b] = 0;
+    ctx->grad_rows[b] = 0;
+  }
+  int rc = eval_pred_impl<T>(ctx, req, out_pred, out_complete);
+  if (rc != SR_OK) return rc;
+  if (nt == 0) return SR_OK;
+  SrProgramBatch<T> prog;
+  std::string err;
+  rc = sr_compile_batch<T>(*trees, ops, n_eval, ds->nf, true, &prog, &err, nullptr, nullptr);
+  if (rc != SR_OK) return set_error(rc, err);
+  // tree t's tangents and where its [n_grad_t][n_eval] block starts in out_grad
+  auto n_grad = [&](int64_t t) -> uint32_t {
+    return mode == kRowGradConsts ? prog.n_consts[size_t(t)] : (mode == kRowGradFeatures ? uint32_t(ds->nf) : 1u);
+  };
+  std::vector<size_t> goff(size_t(nt) + 1, 0);
+  for (int64_t t = 0; t < nt; ++t) goff[size_t(t) + 1] = goff[size_t(t)] + size_t(n_grad(t)) * size_t(n_eval);
+  T* g = static_cast<T*>(out_grad);
+  auto zero_tree = [&](int64_t t) { std::fill(g + goff[size_t(t)], g + goff[size_t(t) + 1], T(0)); };
+  const T* vals = static_cast<const T*>(trees->val);
+  std::vector<T> consts;
+  consts.reserve(size_t(prog.const_off[size_t(nt)]));
+  for (int64_t t = 0; t < nt; ++t)
+    for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i)
+      if (trees->degree[i] == 0 && trees->constant[i]) consts.push_back(vals[i]);
+  // work items in tree order: (tree, first tangent, tangents of the window that are the tree's, bucket)
+  struct Item { uint32_t t, k0, nq; int b; };
+  std::vector<Item> all;
+  for (int64_t t = 0; t < nt; ++t) {
+    const uint32_t ng = n_grad(t);
+    if (ng == 0) continue;
+    if (!out_complete[t]) {
+      zero_tree(t);
+      continue;
+    }
+    if (prog.n_consts[size_t(t)] > 128) return set_error(SR_ERR_TOO_DEEP, "more than 128 constants in one tree");
+    if (mode == kRowGradDiff) {
+      all.push_back(Item{uint32_t(t), uint32_t(direction[t] - 1), 1u, 0});
+      continue;
+    }
+    const int b = ng <= 1 ? 0 : (ng <= 2 ? 1 : (ng <= 4 ? 2 : (ng <= 8 ? 3 : 4)));
+    for (uint32_t k0 = 0; k0 < ng; k0 += uint32_t(kts[b]))
+      all.push_back(Item{uint32_t(t), k0, std::min<uint32_t>(uint32_t(kts[b]), ng - k0), b});
+  }
+  if (all.empty()) return SR_OK;
+  // rows per lane per bucket, over the call's deepest program of that bucket (so they do not depend on the
+  // chunking either); the tile stages X alone (y's place is kept, no weights)
+  int bdepth[kNB] = {1, 1, 1, 1, 1}, rows[kNB] = {};
+  bool used[kNB] = {};
+  for (const Item& it : all) {
+    used[it.b] = true;
+    bdepth[it.b] = std::max(bdepth[it.b], int(prog.depth[it.t]));
+  }
+  for (int b = 0; b < kNB; ++b) {
+    if (!used[b]) continue;
+    rows[b] = sr_grad_launch_rows(int(sizeof(T)), kts[b], int(ds->nf), false, bdepth[b], kWaves, kLdsMax, ctx->grad_rows_force);
+    if (rows[b] == 0)
+      return set_error(SR_ERR_INVALID_ARG, "per-row derivatives: " + std::to_string(ds->nf) + " features and operand stacks of depth " +
+                                               std::to_string(bdepth[b]) + " need more than 160 KiB of LDS at one row per lane");
+    ctx->grad_rows[b] = rows[b];
+  }
+  hipStream_t s = ctx->stream;
+  if (gather) {
+    SR_HIP_CHECK(ctx->row_idx.ensure(size_t(req.n_idx) * sizeof(int64_t)));
+    SR_HIP_CHECK(hipMemcpyAsync(ctx->row_idx.p, req.row_idx, size_t(req.n_idx) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  }
+  // the programs and constants: one image, uploaded once
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t o_code = 0;
+  const size_t o_offs = al(o_code + prog.code.size() * sizeof(SrIns<T>));
+  const size_t o_cons = al(o_offs + prog.offsets.size() * sizeof(uint32_t));
+  const size_t o_coff = al(o_cons + consts.size() * sizeof(T));
+  const size_t prog_bytes = al(o_coff + prog.const_off.size() * sizeof(uint32_t));
+  SR_HIP_CHECK(ctx->g_code.ensure(prog_bytes + 16));
+  SR_HIP_CHECK(ctx->h_grad.ensure(prog_bytes + 16, s, ctx->stream2));
+  {
+    char* hs = ctx->h_grad.as<char>();
+    if (!prog.code.empty()) std::memcpy(hs + o_code, prog.code.data(), prog.code.size() * sizeof(SrIns<T>));
+    std::memcpy(hs + o_offs, prog.offsets.data(), prog.offsets.size() * sizeof(uint32_t));
+    if (!consts.empty()) std::memcpy(hs + o_cons, consts.data(), consts.size() * sizeof(T));
+    std::memcpy(hs + o_coff, prog.const_off.data(), prog.const_off.size() * sizeof(uint32_t));
+    SR_HIP_CHECK(hipMemcpyAsync(ctx->g_code.p, hs, prog_bytes, hipMemcpyHostToDevice, s));
+    SR_HIP_CHECK(hipStreamSynchronize(s));  // (the chunks below reuse no part of h_grad, but it may grow elsewhere)
+  }
+  const char* dprog = ctx->g_code.as<char>();
+  // row blocks as the gradient call's: units of 512 rows
+  constexpr int64_t kUnit = 512;
+  const int64_t n_units = (n_eval + kUnit - 1) / kUnit;
+  const size_t chunk_elems = std::max<size_t>(size_t(ctx->grad_stage_bytes) / sizeof(T), 1);
+  std::vector<uint8_t> tree_bad(size_t(nt), 0);
+  std::vector<uint32_t> himg, hbad;
+  for (size_t c0 = 0; c0 < all.size();) {
+    // the chunk: items c0 .. c1 - 1, their outputs packed in item order
+    size_t c1 = c0, elems = 0;
+    while (c1 < all.size() && (c1 == c0 || elems + size_t(all[c1].nq) * size_t(n_eval) <= chunk_elems)) {
+      elems += size_t(all[c1].nq) * size_t(n_eval);
+      ++c1;
+    }
+    std::vector<uint32_t> items[kNB], k0s[kNB], nqs[kNB];
+    std::vector<uint64_t> outs[kNB];
+    std::vector<size_t> src[kNB];  // (the item's index in `all`)
+    {
+      size_t at_out = 0;
+      for (size_t i = c0; i < c1; ++i) {
+        const Item& it = all[i];
+        items[it.b].push_back(it.t);
+        k0s[it.b].push_back(it.k0);
+        nqs[it.b].push_back(it.nq);
+        outs[it.b].push_back(uint64_t(at_out));
+        src[it.b].push_back(i);
+        at_out += size_t(it.nq) * size_t(n_eval);
+      }
+    }
+    // the chunk's image: per bucket {item_out u64 | item_tree | item_k0 | item_nq}
+    size_t o_items[kNB], at = 0, o_bad[kNB], n_bad = 0;
+    struct Launch { int64_t n_rb, tiles_per_block, n_groups; };
+    Launch lc[kNB] = {};
+    for (int b = 0; b < kNB; ++b) {
+      o_items[b] = at;
+      const size_t ni = items[b].size();
+      at = al(at + ni * (sizeof(uint64_t) + 3 * sizeof(uint32_t)));
+      o_bad[b] = n_bad;
+      if (ni == 0) continue;
+      const int64_t n_groups = (int64_t(ni) + kWaves - 1) / kWaves;
+      int64_t n_rb = (4096 + n_groups - 1) / n_groups;
+      if (n_rb > n_units) n_rb = n_units;
+      if (n_rb < 1) n_rb = 1;
+      const int64_t units_per_block = (n_units + n_rb - 1) / n_rb;
+      n_rb = (n_units + units_per_block - 1) / units_per_block;
+      if (n_rb * n_groups > 0x7fffffff) return set_error(SR_ERR_INVALID_ARG, "grid too large");
+      lc[b] = Launch{n_rb, units_per_block * (kUnit / int64_t(sr_grad_tile_rows(rows[b]))), n_groups};
+      n_bad += size_t(n_rb) * ni;
+    }
+    himg.assign(at / sizeof(uint32_t) + 4, 0u);
+    for (int b = 0; b < kNB; ++b) {
+      const size_t ni = items[b].size();
+      if (ni == 0) continue;
+      char* d = reinterpret_cast<char*>(himg.data()) + o_items[b];
+      std::memcpy(d, outs[b].data(), ni * sizeof(uint64_t));
+      uint32_t* u = reinterpret_cast<uint32_t*>(d + ni * sizeof(uint64_t));
+      std::copy(items[b].begin(), items[b].end(), u);
+      std::copy(k0s[b].begin(), k0s[b].end(), u + ni);
+      std::copy(nqs[b].begin(), nqs[b].end(), u + 2 * ni);
+    }
+    SR_HIP_CHECK(ctx->g_items.ensure(at + 16));
+    SR_HIP_CHECK(ctx->g_out.ensure(elems * sizeof(T) + 16));
+    SR_HIP_CHECK(ctx->g_part.ensure(n_bad * sizeof(uint32_t) + 16));
+    SR_HIP_CHECK(hipMemcpyAsync(ctx->g_items.p, himg.data(), at, hipMemcpyHostToDevice, s));
+    SR_HIP_CHECK(hipMemsetAsync(ctx->g_part.p, 0, n_bad * sizeof(uint32_t), s));
+    bool timed[kNB] = {};
+    for (int b = 0; b < kNB; ++b) {
+      const int64_t ni = int64_t(items[b].size());
+      if (ni == 0) continue;
+      SrGradArgs<T> a{};
+      a.code = reinterpret_cast<const SrIns<T>*>(dprog + o_code);
+      a.offsets = reinterpret_cast<const uint32_t*>(dprog + o_offs);
+      a.consts = reinterpret_cast<const T*>(dprog + o_cons);
+      a.const_off = reinterpret_cast<const uint32_t*>(dprog + o_coff);
+      const char* di = ctx->g_items.as<char>() + o_items[b];
+      SrGradRowArgs<T> d{};
+      d.item_out = reinterpret_cast<const uint64_t*>(di);
+      a.item_tree = reinterpret_cast<const uint32_t*>(di + size_t(ni) * sizeof(uint64_t));
+      a.item_k0 = a.item_tree + ni;
+      d.item_nq = a.item_tree + 2 * ni;
+      a.n_items = int(ni);
+      a.X = static_cast<const T*>(ds->X);
+      a.row_idx = gather ? ctx->row_idx.as<int64_t>() : nullptr;
+      a.ld = ds->ld;
+      a.n_rows = n_eval;
+      a.nf = int(ds->nf);
+      a.tiles_per_block = int(lc[b].tiles_per_block);
+      a.n_row_blocks = int(lc[b].n_rb);
+      a.n_groups = int(lc[b].n_groups);
+      a.stack_depth = bdepth[b];
+      d.out = ctx->g_out.as<T>();
+      d.bad = ctx->g_part.as<uint32_t>() + o_bad[b];
+      d.feat = feat ? 1 : 0;
+      if (ctx->timing) SR_HIP_CHECK(hipEventRecord(ctx->ev_g0[b], s));
+      const int nblk = int(lc[b].n_rb * lc[b].n_groups);
+      SR_HIP_CHECK(gather ? (sr_launch_grad_rows_any<T, true>(a, d, kts[b], rows[b], nblk, s))
+                          : (sr_launch_grad_rows_any<T, false>(a, d, kts[b], rows[b], nblk, s)));
+      if (ctx->timing) {
+        SR_HIP_CHECK(hipEventRecord(ctx->ev_g1[b], s));
+        timed[b] = true;
+      }
+      ctx->grad_items[b] += ni;
+      // (algorithmic flops as the gradient call counts them, without the loss epilogue)
+      double per_row = 0.0;
+      const double kt = kts[b];
+      for (uint32_t t : items[b])
+        for (uint32_t i = prog.offsets[t]; i < prog.offsets[t + 1]; ++i) {
+          const uint32_t opc = prog.code[i].op & SR_OP_MASK;
+          if (opc >= SR_OP_BINARY0) per_row += 3.0 + 2.0 * kt;
+          else if (opc >= SR_OP_UNARY0 && opc < SR_OP_LOAD_DERIVED) per_row += 2.0 + kt;
+        }
+      ctx->grad_flops[b] += per_row * double(n_eval);
+    }
+    // the chunk's tangents to the caller's array: runs of items whose blocks follow each other there too
+    hbad.assign(n_bad + 1, 0u);
+    SR_HIP_CHECK(hipMemcpyAsync(hbad.data(), ctx->g_part.p, n_bad * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    auto host_off = [&](const Item& it) {
+      return goff[it.t] + (mode == kRowGradDiff ? size_t(0) : size_t(it.k0) * size_t(n_eval));
+    };
+    {
+      size_t dev0 = 0, dev_at = 0, h0 = host_off(all[c0]), h_at = h0;
+      for (size_t i = c0; i <= c1; ++i) {
+        if (i == c1 || host_off(all[i]) != h_at) {
+          if (dev_at > dev0)
+            SR_HIP_CHECK(hipMemcpyAsync(g + h0, ctx->g_out.as<T>() + dev0, (dev_at - dev0) * sizeof(T), hipMemcpyDeviceToHost, s));
+          if (i == c1) break;
+          dev0 = dev_at;
+          h0 = h_at = host_off(all[i]);
+        }
+        const size_t ne = size_t(all[i].nq) * size_t(n_eval);
+        dev_at += ne;
+        h_at += ne;
+      }
+    }
+    SR_HIP_CHECK(hipStreamSynchronize(s));
+    for (int b = 0; b < kNB; ++b) {
+      float m = 0.f;
+      if (timed[b] && hipEventElapsedTime(&m, ctx->ev_g0[b], ctx->ev_g1[b]) == hipSuccess) ctx->grad_ms_done[b] += double(m);
+      const size_t ni = items[b].size();
+      for (int64_t r = 0; r < lc[b].n_rb; ++r)
+        for (size_t i = 0; i < ni; ++i)
+          if (hbad[o_bad[b] + size_t(r) * ni + i]) tree_bad[items[b][i]] = 1;
+    }
+    c0 = c1;
+  }
+  // a tree with a non-finite derivative element is incomplete: its derivatives are zero, as an
+  // incomplete tree's gradient is
+  for (int64_t t = 0; t < nt; ++t)
+    if (tree_bad[size_t(t)]) {
+      out_complete[t] = 0;
+      zero_tree(t);
+    }
   return SR_OK;
 }
 
@@ -4334,6 +4603,41 @@ int sr_eval_tree_array_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_i
   return eval_entry(ctx, req, kEvalPred, true, out_pred, nullptr, out_complete);
 }
 
+namespace {
+// the per-row derivative calls' refusals, the lock, the device, then the call for the dataset's type
+int row_grad_entry(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, const int64_t* row_idx,
+                   int64_t n_idx, int mode, const int32_t* direction, void* out_pred, void* out_grad, uint8_t* out_complete) {
+  int rc = validate_common(ctx, ds, opset_id, trees);
+  if (rc != SR_OK) return rc;
+  if (trees->n_trees > 0 && (!out_pred || !out_grad || !out_complete)) return set_error(SR_ERR_INVALID_ARG, "NULL output buffers");
+  if (mode == kRowGradDiff) {
+    if (trees->n_trees > 0 && !direction) return set_error(SR_ERR_INVALID_ARG, "NULL direction");
+    for (int64_t t = 0; t < trees->n_trees; ++t)
+      if (direction[t] < 1 || int64_t(direction[t]) > ds->nf)
+        return set_error(SR_ERR_INVALID_ARG, "tree " + std::to_string(t) + ": direction " + std::to_string(direction[t]) +
+                                                 " outside 1.." + std::to_string(ds->nf));
+  }
+  EvalReq req{ds, opset_id, trees, nullptr, row_idx, n_idx, nullptr, SR_LOSS_L2DIST};
+  Lock l(ctx);
+  SR_HIP_CHECK(hipSetDevice(ctx->device));
+  return ds->dtype == SR_DTYPE_F32 ? eval_row_grad_impl<float>(ctx, req, mode, direction, out_pred, out_grad, out_complete)
+                                   : eval_row_grad_impl<double>(ctx, req, mode, direction, out_pred, out_grad, out_complete);
+}
+}  // namespace
+
+int sr_eval_grad_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                            const int64_t* row_idx, int64_t n_idx, int variable, void* out_pred, void* out_grad,
+                            uint8_t* out_complete) {
+  return row_grad_entry(ctx, ds, opset_id, trees, row_idx, n_idx, variable ? kRowGradFeatures : kRowGradConsts, nullptr,
+                        out_pred, out_grad, out_complete);
+}
+
+int sr_eval_diff_tree_array(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                            const int64_t* row_idx, int64_t n_idx, const int32_t* direction, void* out_pred,
+                            void* out_diff, uint8_t* out_complete) {
+  return row_grad_entry(ctx, ds, opset_id, trees, row_idx, n_idx, kRowGradDiff, direction, out_pred, out_diff, out_complete);
+}
+
 int sr_eval_loss_partials(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                           int64_t n_total, int loss_kind, double* out_sum, uint32_t* out_flags, int out_on_device) {
   if (loss_kind >= kLossExprBase) return set_error(SR_ERR_INVALID_ARG, kLossExprOnly);
@@ -4871,7 +5175,8 @@ int sr_last_grad_info(sr_ctx* ctx, int n, double* kernel_ms, double* flops, int6
   for (int b = 0; b < n && b < sr_ctx::kGradBuckets; ++b) {
     float m = 0.f;
     if (kernel_ms)
-      kernel_ms[b] = (ctx->grad_timed[b] && hipEventElapsedTime(&m, ctx->ev_g0[b], ctx->ev_g1[b]) == hipSuccess) ? double(m) : 0.0;
+      kernel_ms[b] = ctx->grad_ms_done[b] +
+                     ((ctx->grad_timed[b] && hipEventElapsedTime(&m, ctx->ev_g0[b], ctx->ev_g1[b]) == hipSuccess) ? double(m) : 0.0);
     if (flops) flops[b] = ctx->grad_flops[b];
     if (items) items[b] = ctx->grad_items[b];
     if (rows_per_lane) rows_per_lane[b] = ctx->grad_rows[b];

@@ -338,6 +338,22 @@ hipError_t sr_launch_grad_param_any(const SrGradArgs<T>& a, const SrGradParamArg
 template <typename T, bool GATHER>
 hipError_t sr_launch_grad_lossx_any(const SrGradArgs<T>& a, const SrLossProgArgs<T>& x, int kt, int rows, int n_blocks,
                                     hipStream_t s);
+// The per-row build of the gradient kernel (sr_grad_rows_kernel: sr_eval_grad_tree_array,
+// sr_eval_diff_tree_array).  Item i stores tangent k0 + q (q < item_nq[i]) of row r at
+// out[item_out[i] + q * n_rows + r]; bad[row block][item] is 1 when a stored tangent was not finite.
+template <typename T>
+struct SrGradRowArgs {
+  T* out;
+  const uint64_t* item_out;   // [n_items]
+  const uint32_t* item_nq;    // [n_items] the window's tangents that are the tree's (<= KT)
+  uint32_t* bad;              // [n_row_blocks][n_items]
+  int feat;                   // 0: the constants' tangents; 1: the features' (k0 counts features)
+};
+// rows: as sr_launch_grad_any's (sr_grad_launch_rows with weighted = false: y and w are not staged, the
+// tile keeps y's place)
+template <typename T, bool GATHER>
+hipError_t sr_launch_grad_rows_any(const SrGradArgs<T>& a, const SrGradRowArgs<T>& d, int kt, int rows, int n_blocks,
+                                   hipStream_t s);
 // The reference's loss fold in row order for listed trees (sr_fold.h; sr_aux.hip): predictions
 // pred[b][pred_ld] of n rows, losses against y (and w) at row_idx (or the row itself).
 // sr_launch_fold_segsum: per segment of seg_len rows, segsum[b][seg] = the f64 sum of its losses;

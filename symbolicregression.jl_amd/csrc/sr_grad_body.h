@@ -3,6 +3,14 @@
 // sr_grad_param_kernel(a, p), and once with SR_GRAD_LOSSX 1 for sr_grad_lossx_kernel(a, x).  A textual include and not a shared inlined function: the plain kernels
 // then compile from exactly the text they always had (a force-inlined shared body moved their register
 // counts; tools/kernel_resources.py compares them with the parent's).
+// SR_GRAD_ROWOUT 1 (sr_grad_rows_kernel(a, d), sr_eval_grad_tree_array / sr_eval_diff_tree_array): the
+// tangents are not scaled and summed but stored per row, and with d.feat the tangents are the features'
+// (a feature operand x_f carries e_{f-1-k0}, a constant none) instead of the constants'.
+#if SR_GRAD_ROWOUT
+#define SR_GRAD_HOT_SRC 1  // basic_bin: the operand kinds that can carry a one-hot tangent (features too)
+#else
+#define SR_GRAD_HOT_SRC 2
+#endif
   // rows per lane: lane + 64 j, j < R; a staged tile of TROWS rows is interpreted in TROWS / ROWS
   // sub-passes (round 5: one barrier pair and one staging round per 256 rows, not per 64 R; a lane
   // still meets its rows in row order, so the sums are the same bit for bit)
@@ -86,9 +94,21 @@
   if (active && uint32_t(lane) < nconst) cval0 = a.consts[cb + lane];
   if (active && uint32_t(lane) + 64u < nconst) cval1 = a.consts[cb + 64 + lane];
 
+#if SR_GRAD_ROWOUT
+  // where this item's tangents go and how many of the window's KT are the tree's; a non-finite tangent
+  // of a valid row anywhere in the row block
+  uint64_t out0 = 0;
+  int nq = 0;
+  if (active) {
+    out0 = d.item_out[item];
+    nq = int(d.item_nq[item]);
+  }
+  bool any_bad = false;
+#else
   double acc[KT];  // per-lane f64 accumulators across the row block
 #pragma unroll
   for (int k = 0; k < KT; ++k) acc[k] = 0.0;
+#endif
   const bool weighted = a.w != nullptr;
   sr_libm_lds_fill(tid, W * 64);  // libm tables (visible after the first tile's barrier)
 
@@ -100,8 +120,12 @@
       const int64_t v = tile0 + i;
       const int64_t src = GATHER ? ridx[v < a.n_rows ? v : 0] : (v < a.n_rows ? v : 0);
       for (int f = 0; f < a.nf; ++f) xs[f * TROWS + i] = a.X[int64_t(f) * a.ld + src];
+#if !SR_GRAD_ROWOUT
       ys[i] = a.y[src];
       if (weighted) wsv[i] = a.w[src];
+#else
+      (void)weighted;  // (no y, no weights: the tangents go out as they are)
+#endif
     }
     __syncthreads();
     if (!active || pe == pb) continue;
@@ -136,7 +160,14 @@
         auto const_val = [&]() __attribute__((always_inline)) -> T {
           return idx < 64u ? sr_readlane_val<T>(cval0, idx) : sr_readlane_val<T>(cval1, idx - 64u);
         };
-#if !SR_GRAD_PARAM
+#if SR_GRAD_ROWOUT
+        // the leaf operand's own tangent slot: a constant's in constant mode, a feature's (LOAD_FEAT, the
+        // F variants of the binaries) in feature mode, -1 for the other kind (its tangents are zero)
+        const bool feat_operand = opc == SR_OP_LOAD_FEAT || opc == SR_OP_LOAD_FEAT_PUSH ||
+                                  (opc >= SR_OP_BINARY0 && opc < SR_OP_LOAD_PARAM &&
+                                   ((opc - SR_OP_BINARY0) % 6u == SR_V_FL || (opc - SR_OP_BINARY0) % 6u == SR_V_FR));
+        const int jj = feat_operand == (d.feat != 0) ? int(idx) - int(k0) : -1;
+#elif !SR_GRAD_PARAM
         const int jj = int(idx) - int(k0);
 #else
         // (a parameter operand: its tangent's position in the window, -1: not a tangent of this window)
@@ -180,7 +211,7 @@
           if constexpr (SRC == 2) cv = const_val();
           T fix[R] = {};  // constant operand: the tangent at its own slot jj, from the unscaled dv
           T d0[R] = {};
-          const bool hot = SRC >= 2 && jj >= 0 && jj < KT;
+          const bool hot = SRC >= SR_GRAD_HOT_SRC && jj >= 0 && jj < KT;
           if (hot) {
 #pragma unroll
             for (int q = 0; q < KT; ++q)
@@ -219,7 +250,7 @@
             } else {
               // feature (zero tangent) or constant (one-hot at jj): every slot is the tos tangent
               // scaled by its own partial; a constant's own slot adds the constant's partial
-              if (SRC >= 2 && hot) fix[j] = LEFT ? pa + pbv * d0[j] : __builtin_fma(pa, d0[j], pbv);
+              if (SRC >= SR_GRAD_HOT_SRC && hot) fix[j] = LEFT ? pa + pbv * d0[j] : __builtin_fma(pa, d0[j], pbv);
               if constexpr (B == SR_B_ADD) {
                 // scale 1: unchanged
               } else if constexpr (B == SR_B_SUB) {
@@ -235,7 +266,7 @@
               }
             }
           }
-          if (SRC >= 2 && hot) {
+          if (SRC >= SR_GRAD_HOT_SRC && hot) {
 #pragma unroll
             for (int q = 0; q < KT; ++q)
 #pragma unroll
@@ -305,7 +336,11 @@
             for (int j = 0; j < R; ++j) {
               v[j] = xrow[j * 64];
 #pragma unroll
+#if SR_GRAD_ROWOUT
+              for (int q = 0; q < KT; ++q) dv[j][q] = q == jj ? T(1) : T(0);
+#else
               for (int q = 0; q < KT; ++q) dv[j][q] = T(0);
+#endif
             }
             break;
           case SR_OP_LOAD_CONST_PUSH:
@@ -434,7 +469,11 @@
                 if (from_feat) {
                   ov = xrow[j * 64];
 #pragma unroll
+#if SR_GRAD_ROWOUT
+                  for (int q = 0; q < KT; ++q) od[q] = q == jj ? T(1) : T(0);
+#else
                   for (int q = 0; q < KT; ++q) od[q] = T(0);
+#endif
                 } else if (from_stack) {
                   ov = sp[j * 64];
 #pragma unroll
@@ -477,6 +516,24 @@
         }
       }
     }
+#if SR_GRAD_ROWOUT
+    // the tangents themselves, rows fastest: lane l of row group j stores row row0 + 64 j + l, so a
+    // wave's store covers 64 consecutive elements; padded rows and the window's tangents past the tree's
+    // are neither stored nor counted
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int64_t row = row0 + j * 64 + lane;
+      const bool valid = row < a.n_rows;
+#pragma unroll
+      for (int q = 0; q < KT; ++q) {
+        if (q < nq && valid) {
+          const T t = dv[j][q];
+          d.out[out0 + uint64_t(q) * uint64_t(a.n_rows) + uint64_t(row)] = t;
+          any_bad |= !sr_isfinite(t);
+        }
+      }
+    }
+#else
     // d loss / d constant: (d loss / d pred) * d pred / d constant, padded rows excluded
     T coefs[R];
 #if SR_GRAD_LOSSX
@@ -556,14 +613,23 @@
       }
 #endif
     }
+#endif  // !SR_GRAD_ROWOUT
     }  // sub-passes
   }
   if (!active) return;
+#if SR_GRAD_ROWOUT
+  {
+    // one word per (row block, item): lane 0 writes whether any lane met a non-finite tangent
+    const uint64_t m = sr_ballot(any_bad);
+    if (lane == 0) d.bad[size_t(rb) * a.n_items + item] = m ? 1u : 0u;
+  }
+#else
 #pragma unroll
   for (int q = 0; q < KT; ++q) {
     const double s = sr_wave_sum<double>(acc[q]);
     if (lane == 0) a.part[(size_t(rb) * a.n_items + item) * KT + q] = s;
   }
+#endif
 #if SR_GRAD_PARAM
   {
     if (np > 0) {
@@ -584,3 +650,4 @@
     }
   }
 #endif
+#undef SR_GRAD_HOT_SRC

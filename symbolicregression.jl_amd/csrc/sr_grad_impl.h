@@ -127,7 +127,9 @@ template <typename T, int KT, int W, bool GATHER, int R>
 __global__ void __launch_bounds__(W * 64) sr_grad_kernel(const SrGradArgs<T> a) {
 #define SR_GRAD_PARAM 0
 #define SR_GRAD_LOSSX 0
+#define SR_GRAD_ROWOUT 0
 #include "sr_grad_body.h"
+#undef SR_GRAD_ROWOUT
 #undef SR_GRAD_LOSSX
 #undef SR_GRAD_PARAM
 }
@@ -135,7 +137,9 @@ template <typename T, int KT, int W, bool GATHER, int R>
 __global__ void __launch_bounds__(W * 64) sr_grad_param_kernel(const SrGradArgs<T> a, const SrGradParamArgs<T> p) {
 #define SR_GRAD_PARAM 1
 #define SR_GRAD_LOSSX 0
+#define SR_GRAD_ROWOUT 0
 #include "sr_grad_body.h"
+#undef SR_GRAD_ROWOUT
 #undef SR_GRAD_LOSSX
 #undef SR_GRAD_PARAM
 }
@@ -143,7 +147,24 @@ template <typename T, int KT, int W, bool GATHER, int R>
 __global__ void __launch_bounds__(W * 64) sr_grad_lossx_kernel(const SrGradArgs<T> a, const SrLossProgArgs<T> lx) {
 #define SR_GRAD_PARAM 0
 #define SR_GRAD_LOSSX 1
+#define SR_GRAD_ROWOUT 0
 #include "sr_grad_body.h"
+#undef SR_GRAD_ROWOUT
+#undef SR_GRAD_LOSSX
+#undef SR_GRAD_PARAM
+}
+// ROWOUT (sr_grad_rows_kernel, sr_eval_grad_tree_array / sr_eval_diff_tree_array; sr_grad_inst.hip): the same
+// interpreter and rules, no loss: every valid row's tangents are stored ([tangent][row], rows fastest) and a
+// wave ballot records a non-finite one per (row block, item).  d.feat: the tangents are the features' —
+// a feature operand is one-hot in its own slot exactly as a constant operand is in the other builds, and a
+// constant is what a feature is there (zero tangent, the partial x 0 term kept).  y and w are not staged.
+template <typename T, int KT, int W, bool GATHER, int R>
+__global__ void __launch_bounds__(W * 64) sr_grad_rows_kernel(const SrGradArgs<T> a, const SrGradRowArgs<T> d) {
+#define SR_GRAD_PARAM 0
+#define SR_GRAD_LOSSX 0
+#define SR_GRAD_ROWOUT 1
+#include "sr_grad_body.h"
+#undef SR_GRAD_ROWOUT
 #undef SR_GRAD_LOSSX
 #undef SR_GRAD_PARAM
 }
@@ -233,6 +254,41 @@ hipError_t sr_launch_grad_lossx_any(const SrGradArgs<T>& a, const SrLossProgArgs
     case 4: return go(std::integral_constant<int, 4>{});
     case 8: return go(std::integral_constant<int, 8>{});
     case 16: return go(std::integral_constant<int, 16>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The per-row builds: the plain kernel's set of rows per lane (sr_grad_launch_rows picks one; the stored
+// tangents do not depend on it), one translation unit per element type and gather mode (sr_grad_inst.hip).
+template <typename T, int KT, int W, bool GATHER, int R>
+hipError_t sr_launch_grad_rows(const SrGradArgs<T>& a, const SrGradRowArgs<T>& d, int n_blocks, hipStream_t s) {
+  if (d.out == nullptr || d.item_out == nullptr || d.item_nq == nullptr || d.bad == nullptr) return hipErrorInvalidValue;
+  const size_t lds = sr_grad_lds_bytes(int(sizeof(T)), KT, R, a.nf, false, a.stack_depth, W);
+  const void* fn = reinterpret_cast<const void*>(&sr_grad_rows_kernel<T, KT, W, GATHER, R>);
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((sr_grad_rows_kernel<T, KT, W, GATHER, R>), dim3(n_blocks), dim3(W * 64), lds, s, a, d);
+  return hipGetLastError();
+}
+template <typename T, bool GATHER, int KT, int RR>
+hipError_t sr_launch_grad_rows_rows_from(const SrGradArgs<T>& a, const SrGradRowArgs<T>& d, int rows, int n_blocks,
+                                         hipStream_t s) {
+  if (rows == RR) return sr_launch_grad_rows<T, KT, 4, GATHER, RR>(a, d, n_blocks, s);
+  if constexpr (RR > 1) return sr_launch_grad_rows_rows_from<T, GATHER, KT, RR / 2>(a, d, rows, n_blocks, s);
+  return hipErrorInvalidValue;
+}
+template <typename T, bool GATHER>
+hipError_t sr_launch_grad_rows_any(const SrGradArgs<T>& a, const SrGradRowArgs<T>& d, int kt, int rows, int n_blocks,
+                                   hipStream_t s) {
+  if (a.w != nullptr) return hipErrorInvalidValue;  // (the tile holds no weights: sr_launch_grad_rows' LDS size)
+  switch (kt) {
+    case 1: return sr_launch_grad_rows_rows_from<T, GATHER, 1, sr_grad_rows_per_lane(1)>(a, d, rows, n_blocks, s);
+    case 2: return sr_launch_grad_rows_rows_from<T, GATHER, 2, sr_grad_rows_per_lane(2)>(a, d, rows, n_blocks, s);
+    case 4: return sr_launch_grad_rows_rows_from<T, GATHER, 4, sr_grad_rows_per_lane(4)>(a, d, rows, n_blocks, s);
+    case 8: return sr_launch_grad_rows_rows_from<T, GATHER, 8, sr_grad_rows_per_lane(8)>(a, d, rows, n_blocks, s);
+    case 16: return sr_launch_grad_rows_rows_from<T, GATHER, 16, sr_grad_rows_per_lane(16)>(a, d, rows, n_blocks, s);
     default: return hipErrorInvalidValue;
   }
 }

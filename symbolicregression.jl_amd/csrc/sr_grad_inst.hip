@@ -14,6 +14,10 @@
 #define SR_GRAD_LOSSX(T, GATHER)                                                                                         \
   template hipError_t sr_launch_grad_lossx_any<T, GATHER>(const SrGradArgs<T>&, const SrLossProgArgs<T>&, int, int, int, \
                                                           hipStream_t);
+// the per-row tangent kernels (ROWOUT): tangent widths 1 - 16 at the plain kernels' rows per lane
+#define SR_GRAD_ROWS(T, GATHER)                                                                                        \
+  template hipError_t sr_launch_grad_rows_any<T, GATHER>(const SrGradArgs<T>&, const SrGradRowArgs<T>&, int, int, int, \
+                                                         hipStream_t);
 // the Float64 forward-mode constant-gradient kernels
 #define SR_GRAD_UNIT_f64 template hipError_t sr_launch_grad_any<double>(const SrGradArgs<double>&, int, bool, int, int, hipStream_t);
 // full view / gathered row views
@@ -25,6 +29,10 @@
 #define SR_GRAD_UNIT_lossx_f32_gather SR_GRAD_LOSSX(float, true)
 #define SR_GRAD_UNIT_lossx_f64_full SR_GRAD_LOSSX(double, false)
 #define SR_GRAD_UNIT_lossx_f64_gather SR_GRAD_LOSSX(double, true)
+#define SR_GRAD_UNIT_rows_f32_full SR_GRAD_ROWS(float, false)
+#define SR_GRAD_UNIT_rows_f32_gather SR_GRAD_ROWS(float, true)
+#define SR_GRAD_UNIT_rows_f64_full SR_GRAD_ROWS(double, false)
+#define SR_GRAD_UNIT_rows_f64_gather SR_GRAD_ROWS(double, true)
 
 #define SR_GRAD_INST_(unit) SR_GRAD_UNIT_##unit
 #define SR_GRAD_INST(unit) SR_GRAD_INST_(unit)

@@ -53,6 +53,10 @@ struct SrKnobs {
   int grad_rows_force = 0;  // SR_AMD_GRAD_ROWS / "grad_rows": the gradient kernel's rows per lane (0: chosen per call)
   int grad_sort = 1;        // SR_AMD_GRAD_SORT / "grad_sort": gradient work items ordered by program cost
   int grad_lane_bins = 1;   // "grad_lane_bins": parametric gradients bin small slots x classes per lane (sr_eval.h)
+  // "grad_stage_bytes": device staging of the per-row derivative calls (sr_eval_grad_tree_array / _diff_): work
+  // items go out in chunks whose tangents stay within this many bytes, one item's own output when that is
+  // larger; results do not depend on it
+  int64_t grad_stage_bytes = int64_t(256) << 20;
   int first_chunk = 6;       // SR_AMD_FIRST_CHUNK: the two-chunk pipeline's first chunk is 1/first_chunk
   int64_t chunk_min = 1024;  // SR_AMD_CHUNK_MIN: the two-chunk pipeline runs when its first chunk holds this many trees
   int inject_fail = 0;         // tests ("inject_failure"): the next k collective-buffer growths fail
@@ -193,6 +197,7 @@ constexpr SrKnobRow kSrKnobs[] = {
     {"grad_rows", "SR_AMD_GRAD_ROWS", &SrKnobs::grad_rows_force},
     {"grad_sort", "SR_AMD_GRAD_SORT", &SrKnobs::grad_sort, SR_KNOB_FLAG},
     {"grad_lane_bins", nullptr, &SrKnobs::grad_lane_bins, SR_KNOB_FLAG},
+    {"grad_stage_bytes", nullptr, &SrKnobs::grad_stage_bytes, 1, kKnobMax},
     // the in-order loss fold
     {"ref_fold", "SR_AMD_REF_FOLD", &SrKnobs::ref_fold, SR_KNOB_FLAG},
     {"fold_seg", "SR_AMD_FOLD_SEG", &SrKnobs::fold_seg, -1, kKnobMax},

@@ -395,6 +395,61 @@ function eval_grad_batch(trees::AbstractVector, dataset::Dataset{T,L}, options::
     return L.(losses), grads[1:end-1], complete .== 0x01
 end
 
+"""`eval_grad_tree_array(tree, X, options; variable)` on the device
+(src/InterfaceDynamicExpressions.jl:153-165): `(evaluation, gradient, complete)`, or `nothing` when the
+device cannot take the tree.  The library writes `[n_grad][n]` with rows fastest; Julia's `dx` is
+`n_gradients × n` column-major, so the result is the transpose view of the `n × n_grad` buffer."""
+function eval_grad_tree_array_device(tree, dataset::Dataset{T}, options::AbstractOptions; variable::Bool=false) where {T}
+    device_tree(tree) || return nothing
+    ctx = context()
+    oid = opset_id(ctx, get_operators(tree, options))
+    oid === nothing && return nothing
+    f = flatten([tree], T)
+    n = dataset.n
+    n_grad = variable ? dataset.nfeatures : count(==(0x01), f.constant)
+    out = Vector{T}(undef, n)
+    grads = zeros(T, n, max(n_grad, 1))
+    complete = Vector{UInt8}(undef, 1)
+    dsh = device_dataset(ctx, dataset)
+    GC.@preserve f out grads complete begin
+        b = SrTreeBatch(1, pointer(f.offsets), pointer(f.degree), pointer(f.op),
+                        pointer(f.feature), pointer(f.constant), Ptr{Cvoid}(pointer(f.val)))
+        rc = ccall((:sr_eval_grad_tree_array, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{SrTreeBatch}, Ptr{Int64}, Int64, Cint, Ptr{T}, Ptr{T}, Ptr{UInt8}),
+                   ctx.handle, dsh, oid, b, C_NULL, 0, variable ? 1 : 0, out, grads, complete)
+        rc == SR_ERR_UNSUPPORTED_OP && return nothing
+        check(rc)
+    end
+    return out, transpose(view(grads, :, 1:n_grad)), complete[1] == 0x01
+end
+
+"""`eval_diff_tree_array(tree, X, options, direction)` on the device
+(src/InterfaceDynamicExpressions.jl:118-130): `(evaluation, derivative, complete)` with respect to feature
+`direction` (1-based, as in the reference), or `nothing` when the device cannot take the tree."""
+function eval_diff_tree_array_device(tree, dataset::Dataset{T}, options::AbstractOptions, direction::Integer) where {T}
+    device_tree(tree) || return nothing
+    ctx = context()
+    oid = opset_id(ctx, get_operators(tree, options))
+    oid === nothing && return nothing
+    f = flatten([tree], T)
+    n = dataset.n
+    out = Vector{T}(undef, n)
+    diff = zeros(T, n)
+    complete = Vector{UInt8}(undef, 1)
+    dir = Int32[direction]
+    dsh = device_dataset(ctx, dataset)
+    GC.@preserve f out diff complete dir begin
+        b = SrTreeBatch(1, pointer(f.offsets), pointer(f.degree), pointer(f.op),
+                        pointer(f.feature), pointer(f.constant), Ptr{Cvoid}(pointer(f.val)))
+        rc = ccall((:sr_eval_diff_tree_array, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{SrTreeBatch}, Ptr{Int64}, Int64, Ptr{Int32}, Ptr{T}, Ptr{T}, Ptr{UInt8}),
+                   ctx.handle, dsh, oid, b, C_NULL, 0, dir, out, diff, complete)
+        rc == SR_ERR_UNSUPPORTED_OP && return nothing
+        check(rc)
+    end
+    return out, diff, complete[1] == 0x01
+end
+
 """Batched `eval_cost` (src/LossFunctions.jl:193-209): fills `costs`, `losses` in place
 (`loss_to_cost` on the host, exactly as the reference).  Falls back to the reference's own
 `eval_cost` per member when the device cannot evaluate the trees."""

@@ -10,6 +10,12 @@ from ._lib import SRError, UnsupportedOperatorError
 from .constant_optimization import optimize_constants_batch
 from .dataset import Dataset, SubDataset, batch
 from .device import DeviceContext, device_available, get_context
+from .diff import (
+    eval_diff_tree_array,
+    eval_diff_tree_array_batch,
+    eval_grad_tree_array,
+    eval_grad_tree_array_batch,
+)
 from .loss import (
     compute_complexity,
     eval_cost,
@@ -47,6 +53,7 @@ __all__ = [
     "Options", "OperatorEnum", "Dataset", "SubDataset", "batch", "Node", "TreeBatch", "flatten_trees",
     "extend_operators", "apply_unary", "apply_binary", "parse_expression", "string_tree",
     "get_scalar_constants", "set_scalar_constants", "eval_tree_array", "eval_tree_array_batch",
+    "eval_diff_tree_array", "eval_grad_tree_array", "eval_diff_tree_array_batch", "eval_grad_tree_array_batch",
     "eval_loss", "eval_loss_batch", "eval_grad_batch", "eval_loss_batch_views", "eval_grad_batch_views", "eval_cost", "eval_cost_batch", "loss_to_cost",
     "update_baseline_loss_", "score_func", "compute_complexity", "gen_random_tree_fixed_size",
     "gen_random_population", "gen_random_batch", "make_random_leaf", "get_context", "device_available", "DeviceContext",

@@ -105,6 +105,8 @@ EXPORTED_SYMBOLS = (
     "sr_loss_expr_host",
     "sr_compile_info_grad",
     "sr_compile_info_grad_parametric",
+    "sr_eval_grad_tree_array",
+    "sr_eval_diff_tree_array",
 )
 
 # mutation kinds in sr_search_options.mutation_weights order (SR_MUT_*)
@@ -227,6 +229,8 @@ def _load():
             [P, P, c_int, POINTER(SrTreeBatch), P, c_int, P, c_int64, c_int, P, P, P],
         ),
         "sr_eval_tree_array": (c_int, [P, P, c_int, POINTER(SrTreeBatch), P, c_int64, P, P]),
+        "sr_eval_grad_tree_array": (c_int, [P, P, c_int, POINTER(SrTreeBatch), P, c_int64, c_int, P, P, P]),
+        "sr_eval_diff_tree_array": (c_int, [P, P, c_int, POINTER(SrTreeBatch), P, c_int64, P, P, P, P]),
         "sr_eval_loss_batch_parametric": (
             c_int,
             [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), P, c_int64, c_int, P, P],

@@ -94,7 +94,8 @@ class DeviceContext:
         "exact_early" (a multi-chunk call's exact-sum pass runs beside the last fold chains: 1 default) — the
         two at 0: the two-chunk launch sequence; "chunk_min" / "first_chunk" (the chunks' smallest size and
         the first chunk's share); "grad_rows" / "grad_sort" (the gradient kernel's rows per lane and work-item
-        order: results do not depend on them), "grad_lane_bins" (parametric gradients: per-lane class
+        order: results do not depend on them), "grad_stage_bytes" (the per-row derivative calls' device staging per
+        chunk of work items, 256 MiB default: results do not depend on it), "grad_lane_bins" (parametric gradients: per-lane class
         accumulators where slots x classes <= 16, 1 default; 0 = masked wave sums everywhere — the two differ
         in the last bits); tests:
         "inject_failure*", "debug_hint_regrow", "fold_debug_fail"."""

@@ -52,6 +52,7 @@ void check_defaults() {
   CHECK(k.grad_rows_force == 0);
   CHECK(k.grad_sort == 1);
   CHECK(k.grad_lane_bins == 1);
+  CHECK(k.grad_stage_bytes == (int64_t(256) << 20));
   CHECK(k.first_chunk == 6);
   CHECK(k.chunk_min == 1024);
   CHECK(k.inject_fail == 0 && k.inject_post == 0 && k.inject_post_exact == 0 && k.inject_post_gather == 0 &&
@@ -97,6 +98,7 @@ const Expect kExpect[] = {
     {"derived", GET(derived), FLAG, nullptr},
     {"grad_lane_bins", GET(grad_lane_bins), FLAG, nullptr},
     {"grad_sort", GET(grad_sort), FLAG, nullptr},
+    {"grad_stage_bytes", GET(grad_stage_bytes), {1, 1, 1, 2, 7, 100, B}, nullptr},
     {"chunk_min", GET(chunk_min), {1, 1, 1, 2, 7, 100, B}, nullptr},
     {"first_chunk", GET(first_chunk), {2, 2, 2, 2, 7, 64, 64}, nullptr},
     {"max_row_blocks", GET(max_row_blocks), {1, 1, 1, 2, 7, 100, 65536}, nullptr},
