@@ -442,6 +442,14 @@ int sr_compile_info_grad_parametric(int dtype, int n_unary, const char* const* u
  */
 int sr_host_unary(int dtype, const char* name, int64_t n, const void* x, void* out);
 
+/*
+ * Host-side evaluation of one catalog loss (SR_LOSS_* kind, its parameter) at n points of dtype: the functions
+ * the device kernels run, out_value[i] = loss(pred[i], target[i]) and out_deriv[i] = d loss / d pred there.  The
+ * parameter is rounded to dtype, as a scoring call rounds it.  For testing host/device agreement.
+ */
+int sr_host_elem_loss(int dtype, int kind, double param, int64_t n, const void* pred, const void* target,
+                      void* out_value, void* out_deriv);
+
 /* ------------------------------------------------------------------ native search engine
  * equation_search's inner loop (s_r_cycle, optimize_and_simplify_population, the head's per-island
  * bookkeeping: src/SingleIteration.jl, src/RegularizedEvolution.jl, src/Mutate.jl,

@@ -207,6 +207,10 @@ __global__ void __launch_bounds__(256) sr_fold_segsum_kernel(SrFoldRows<T> rows,
   SrFoldRows<T> rw = rows;
   rw.pr = rows.pr + int64_t(b) * pred_ld;
   const int64_t lo = int64_t(seg) * seg_len, hi = lo + seg_len < n ? lo + seg_len : n;
+  if (sizeof(T) == 4) {  // Float32 log / cos (Logit, Periodic) read sr_libm.h's tables from the workgroup's LDS copy
+    sr_libm_lds_fill(tid, 256);
+    __syncthreads();
+  }
   double acc = 0.0;
   for (int64_t i = lo + tid; i < hi; i += 256) acc += double(rw(i));
   __shared__ double s_w[4];
@@ -231,6 +235,10 @@ __global__ void __launch_bounds__(256) sr_fold_segtab_kernel(SrFoldRows<T> rows,
   rw.pr = rows.pr + int64_t(b) * pred_ld;
   __shared__ double s_d[4];
   __shared__ I s_v[4][4];
+  if (sizeof(T) == 4) {  // Float32 log / cos (Logit, Periodic) read sr_libm.h's tables from the workgroup's LDS copy
+    sr_libm_lds_fill(tid, 256);
+    __syncthreads();
+  }
   // the f64 prefix before this segment (any order: it only chooses the binades to tabulate)
   const double* ss = segsum + int64_t(b) * n_seg;
   double pre = 0.0;
@@ -433,6 +441,10 @@ __global__ void __launch_bounds__(1024) sr_fold_chain_kernel(SrFoldRows<T> rows,
   const int b = int(blockIdx.x), tid = int(threadIdx.x);
   SrFoldRows<T> rw = rows;
   rw.pr = rows.pr + int64_t(b) * pred_ld;
+  if (sizeof(T) == 4) {  // Float32 log / cos (Logit, Periodic) read sr_libm.h's tables from the workgroup's LDS copy
+    sr_libm_lds_fill(tid, 1024);
+    __syncthreads();
+  }
   if (tid == 0) {
     if (carry) {
       s_p = carry[b];

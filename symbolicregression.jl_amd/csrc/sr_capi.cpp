@@ -4289,10 +4289,29 @@ int sr_register_opset(sr_ctx* ctx, int n_unary, const char* const* unary_names, 
   return SR_OK;
 }
 
+extern "C++" {
+namespace {
+// The parameter's domain per loss: delta (Huber), eps (both EpsilonIns), circ (Periodic), gamma (SmoothedL1Hinge),
+// q (DWDMargin) and P (LPDist) positive; tau (Quantile) unbounded.  LossFunctions' constructors assert these, as
+// far as memory of a package that is not vendored goes; circ and gamma are divisors in sr_elem_loss, so 0 is
+// refused whatever the package does.
+bool loss_param_in_domain(int kind, double param) {
+  switch (kind) {
+    case SR_LOSS_LP: case SR_LOSS_HUBER: case SR_LOSS_L1_EPS_INS: case SR_LOSS_L2_EPS_INS: case SR_LOSS_PERIODIC:
+    case SR_LOSS_SMOOTH_L1_HINGE: case SR_LOSS_DWD_MARGIN:
+      return param > 0.0;
+    default: return true;
+  }
+}
+}  // namespace
+}
+
 int sr_register_loss(sr_ctx* ctx, int kind, double param, int* loss_code) {
   if (check_ctx(ctx) != SR_OK) return SR_ERR_INVALID_ARG;
   if (!loss_code || kind < 0 || kind >= SR_LOSS_COUNT) return set_error(SR_ERR_INVALID_ARG, "unknown loss kind");
   if (!std::isfinite(param)) return set_error(SR_ERR_INVALID_ARG, "loss parameter must be finite");
+  if (!loss_param_in_domain(kind, param))
+    return set_error(SR_ERR_INVALID_ARG, "loss parameter outside the loss's domain (delta, eps, circ, gamma, q, P must be positive)");
   Lock l(ctx);
   for (size_t i = 0; i < ctx->losses.size(); ++i)
     if (ctx->losses[i].first == kind && ctx->losses[i].second == param) {
@@ -5079,6 +5098,30 @@ int sr_host_unary(int dtype, const char* name, int64_t n, const void* x, void* o
     for (int64_t i = 0; i < n; ++i) static_cast<float*>(out)[i] = sr_unary<float>(id, static_cast<const float*>(x)[i]);
   } else if (dtype == SR_DTYPE_F64) {
     for (int64_t i = 0; i < n; ++i) static_cast<double*>(out)[i] = sr_unary<double>(id, static_cast<const double*>(x)[i]);
+  } else {
+    return set_error(SR_ERR_INVALID_ARG, "unknown dtype");
+  }
+  return SR_OK;
+}
+
+int sr_host_elem_loss(int dtype, int kind, double param, int64_t n, const void* pred, const void* target,
+                      void* out_value, void* out_deriv) {
+  if (kind < 0 || kind >= SR_LOSS_COUNT) return set_error(SR_ERR_INVALID_ARG, "unknown loss kind");
+  if (n < 0 || (n > 0 && (!pred || !target || !out_value || !out_deriv))) return set_error(SR_ERR_INVALID_ARG, "bad arguments");
+  if (dtype == SR_DTYPE_F32) {
+    const float* p = static_cast<const float*>(pred);
+    const float* t = static_cast<const float*>(target);
+    for (int64_t i = 0; i < n; ++i) {
+      static_cast<float*>(out_value)[i] = sr_elem_loss<float>(kind, p[i], t[i], float(param));
+      static_cast<float*>(out_deriv)[i] = sr_elem_loss_deriv<float>(kind, p[i], t[i], float(param));
+    }
+  } else if (dtype == SR_DTYPE_F64) {
+    const double* p = static_cast<const double*>(pred);
+    const double* t = static_cast<const double*>(target);
+    for (int64_t i = 0; i < n; ++i) {
+      static_cast<double*>(out_value)[i] = sr_elem_loss<double>(kind, p[i], t[i], param);
+      static_cast<double*>(out_deriv)[i] = sr_elem_loss_deriv<double>(kind, p[i], t[i], param);
+    }
   } else {
     return set_error(SR_ERR_INVALID_ARG, "unknown dtype");
   }

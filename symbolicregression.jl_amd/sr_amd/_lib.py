@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "sr_eval_grad_batch_views",
     "sr_compile_info",
     "sr_host_unary",
+    "sr_host_elem_loss",
     "sr_last_kernel_ms",
     "sr_last_phase_ms",
     "sr_set_tuning",
@@ -311,6 +312,7 @@ def _load():
              c_int64, c_int64, P, P, POINTER(c_int), P, c_int64],
         ),
         "sr_host_unary": (c_int, [c_int, c_char_p, c_int64, P, P]),
+        "sr_host_elem_loss": (c_int, [c_int, c_int, c_double, c_int64, P, P, P, P]),
         "sr_last_kernel_ms": (c_int, [P, POINTER(c_double), POINTER(c_double)]),
         "sr_last_phase_ms": (c_int, [P, POINTER(c_double), c_int]),
         "sr_set_tuning": (c_int, [P, ctypes.c_char_p, ctypes.c_int64]),

@@ -28,6 +28,10 @@ LOSS_KINDS = {
 }
 LOSS_DEFAULTS = {"HuberLoss": 1.0}  # LossFunctions' HuberLoss() default delta
 LOSSES = {"l2": 0, "l1": 1}  # short aliases
+# Parameters that must be positive (sr_register_loss refuses the same): every one but QuantileLoss's tau.
+# LossFunctions' constructors assert these as far as memory of the package goes (it is not vendored); circ and
+# gamma are divisors of the device formulas, so 0 is refused whatever the package does.
+LOSS_POSITIVE = ("P", "d", "eps", "circ", "gamma", "q")
 
 
 def parse_loss(spec):
@@ -50,7 +54,10 @@ def parse_loss(spec):
         if name not in LOSS_DEFAULTS:
             raise ValueError(f"{name} needs its parameter {pname}, e.g. {name}(1.0)")
         return kind, LOSS_DEFAULTS[name]
-    return kind, float(arg)
+    value = float(arg)
+    if not np.isfinite(value) or (pname in LOSS_POSITIVE and not value > 0):
+        raise ValueError(f"{name}: the parameter {pname} must be {'positive' if pname in LOSS_POSITIVE else 'finite'}, got {arg}")
+    return kind, value
 
 
 # An elementwise loss given as an expression (include/sr_amd.h sr_register_loss_expr): SrLossKind's

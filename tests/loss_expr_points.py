@@ -475,11 +475,22 @@ def _dataset(body, p, t, w):
         return Dataset(X, np.ascontiguousarray(t), **(dict(weights=np.ascontiguousarray(w)) if weighted else {})), weighted
 
 
-def _one_row_values(body, ds, n, dtype, tier):
+def one_row_losses(opts, ds, n, dtype):
+    """(loss [n], complete [n]): tree k = x1 on the one-row view [k] of `ds` (also loss_values_util.py's harness)."""
     tb = flatten_trees([Node(feature=1) for _ in range(n)], dtype)  # x1 keeps -0.0
-    loss, comp = eval_loss_batch_views(tb, ds, _options(body, tier), np.arange(n, dtype=np.int32),
-                                       np.arange(n, dtype=np.int64)[:, None])
-    return loss, comp
+    return eval_loss_batch_views(tb, ds, opts, np.arange(n, dtype=np.int32), np.arange(n, dtype=np.int64)[:, None])
+
+
+def one_row_gradients(opts, ds, n, dtype):
+    """(gradient [n], complete [n]): tree k = x1 + 0.0 on the one-row view [k]; its single entry is dL/dp."""
+    tb = flatten_trees([parse_expression("x1 + 0.0", opts) for _ in range(n)], dtype)
+    _, g, gc = eval_grad_batch_views(tb, ds, opts, np.arange(n, dtype=np.int32), np.arange(n, dtype=np.int64)[:, None])
+    assert g.shape == (n,), g.shape
+    return g, gc
+
+
+def _one_row_values(body, ds, n, dtype, tier):
+    return one_row_losses(_options(body, tier), ds, n, dtype)
 
 
 def device_elements(body, p, t, w, dtype, tier, deriv=True):
@@ -502,10 +513,8 @@ def device_elements(body, p, t, w, dtype, tier, deriv=True):
             val[zero] = np.where(inv[zero] < 0, dtype(-0.0), dtype(0.0))
         der = None
         if deriv:
-            opts = _options(body, tier, gradient=True)
-            tb = flatten_trees([parse_expression("x1 + 0.0", opts) for _ in range(n)], dtype)
-            _, g, gc = eval_grad_batch_views(tb, ds, opts, np.arange(n, dtype=np.int32), np.arange(n, dtype=np.int64)[:, None])
-            assert g.shape == (n,) and np.array_equal(gc, comp), (body, gc, comp)
+            g, gc = one_row_gradients(_options(body, tier, gradient=True), ds, n, dtype)
+            assert np.array_equal(gc, comp), (body, gc, comp)
             with np.errstate(all="ignore"):
                 der = (g * scale).astype(dtype)
     finally:

@@ -3,8 +3,9 @@ csrc/sr_ops.h and in the oracle) — every loss against the oracle on random pop
 bit-exact, losses on well-conditioned trees), weighted and SubDataset paths, f64, and the
 forward-mode gradient of the smooth ones against the oracle's finite differences.  Only L2/L1 are
 pinned by reference tests (test/unit/misc/test_losses.jl:15-33, tests/test_oracle_golden.py); the
-others follow the published LossFunctions definitions (parity unpinned beyond the oracle's own
-hand-computed points, test_oracle_golden.py::test_loss_catalog_known_answers).
+others follow the published LossFunctions definitions, pinned per point, kinks included, by
+tests/golden/loss_values.json: test_loss_values_host.py (the oracle, the host functions) and
+test_gpu_loss_values.py (every device path, values and derivatives).
 """
 import numpy as np
 import pytest
