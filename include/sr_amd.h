@@ -437,6 +437,40 @@ int sr_compile_info_grad_parametric(int dtype, int n_unary, const char* const* u
                                     void* out_code, int64_t code_capacity);
 
 /*
+ * Tied and frozen constants (TemplateExpression candidates composed into one tree): a
+ * sub-expression called several times puts each of its constants into the composed tree several times, and
+ * those copies are ONE optimisable scalar; literals of the template's structure are none.
+ *   slot[j], j-th constant node of the whole batch in pre-order: the index of its scalar within its tree's
+ *   scalar vector (0 <= slot < n_scalars[tree]; copies of one scalar share it), or -1 for a frozen constant.
+ */
+typedef struct sr_scalar_ties {
+  const int32_t* slot;       /* per constant node of the batch, pre-order: scalar index within its tree, -1 frozen */
+  const int32_t* n_scalars;  /* per tree */
+} sr_scalar_ties;
+
+/*
+ * sr_eval_grad_batch (params == NULL) / sr_eval_grad_batch_parametric with ties: tree t's gradient holds its
+ * n_scalars[t] scalars' derivatives (each the derivative with respect to the scalar, i.e. over all its
+ * copies), followed by the max_parameters x n_classes parameter entries when params is given.  The gradient
+ * programs are those of the untied calls except that a constant operand's index is its scalar slot (frozen
+ * constants take the indices n_scalars.. of the tree's constant table, which the tangent windows do not
+ * cover).  The limit of 128 is one on table entries (scalars + frozen constants).  A scalar that no constant
+ * node of the tree names (an unread entry of a parameter vector, a sub-expression called only inside a dropped
+ * argument) has derivative exactly 0.  SR_ERR_INVALID_ARG when copies of one scalar hold different values or a
+ * slot is out of range.
+ */
+int sr_eval_grad_batch_tied(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                            const sr_param_batch* params, const sr_scalar_ties* ties, const int64_t* row_idx,
+                            int64_t n_idx, int loss_kind, void* out_loss, void* out_grad, uint8_t* out_complete);
+/* The host dry run of those gradient programs (sr_compile_info_grad's arguments plus params, which may be
+ * NULL, and ties). */
+int sr_compile_info_grad_tied(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                              const char* const* binary_names, const sr_tree_batch* trees,
+                              const sr_param_batch* params, const sr_scalar_ties* ties, int64_t n_rows,
+                              int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
+                              void* out_code, int64_t code_capacity);
+
+/*
  * Host-side evaluation of one unary operator (the code constant folding uses; the device runs the
  * same functions): out[i] = op(x[i]) for n values of dtype.  For testing host/device agreement.
  */
@@ -587,6 +621,21 @@ int sr_optimize_constants_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, in
                                            int loss_kind, int iterations, int64_t f_calls_limit, int nrestarts,
                                            uint64_t seed, void* out_consts, void* out_params, void* out_loss,
                                            uint8_t* out_improved, int64_t* out_f_calls);
+
+/*
+ * The same optimiser (algorithm, restarts and limits unchanged) on each tree's SCALAR vector
+ * x = [its n_scalars scalars; vec(parameters) when params != NULL]: every scalar is written to all its copies
+ * before each loss or gradient call (sr_eval_grad_batch_tied), frozen constants are never touched.
+ * A scalar starts from its copies' common value (SR_ERR_INVALID_ARG when they differ); a scalar that no constant
+ * node names does not move and comes back as 0: the caller keeps its own value for it.
+ * out_scalars: sum_t n_scalars[t] values (unchanged where not improved); out_params as above (may be NULL when
+ * params is).
+ */
+int sr_optimize_constants_batch_tied(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                     const sr_param_batch* params, const sr_scalar_ties* ties, const int64_t* row_idx,
+                                     int64_t n_idx, int loss_kind, int iterations, int64_t f_calls_limit,
+                                     int nrestarts, uint64_t seed, void* out_scalars, void* out_params, void* out_loss,
+                                     uint8_t* out_improved, int64_t* out_f_calls);
 
 /* The same optimiser with the scoring calls answered by CPU callbacks (sr_loss_fn / sr_grad_fn, as
  * sr_search_use_callbacks): a test seam and the host-port baseline.  dtype = the trees' element type. */

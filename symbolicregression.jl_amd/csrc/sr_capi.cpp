@@ -453,6 +453,7 @@ struct EvalReq {
   int64_t n_idx = 0;
   const ViewSpec* views = nullptr;         // several row views in one call; NULL: one view
   int loss_kind = 0;                       // as passed to the eval calls (decode_loss)
+  const sr_scalar_ties* ties = nullptr;    // sr_eval_grad_batch_tied: tied / frozen constants (the gradient only)
   bool gather() const { return row_idx != nullptr && n_idx > 0; }
   int64_t n_eval() const { return gather() ? n_idx : ds->n; }
   // view v alone, as a request of its own (the exact-sum pass and the fallback fold run view by view)
@@ -2759,8 +2760,16 @@ int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_gr
                             int32_t(pK)};
   SrProgramBatch<T> prog;
   std::string err;
-  rc = sr_compile_batch<T>(*trees, ops, n_eval, ds->nf, true, &prog, &err, nullptr, parametric ? &pnodes : nullptr);
+  const sr_scalar_ties* const ties = req.ties;
+  rc = sr_compile_batch<T>(*trees, ops, n_eval, ds->nf, true, &prog, &err, nullptr, parametric ? &pnodes : nullptr, ties);
   if (rc != SR_OK) return set_error(rc, err);
+  // tree t's differentiated scalars: its constants, or with ties its n_scalars (prog.n_consts then counts the
+  // constant table's entries: the scalars, then the frozen constants)
+  std::vector<uint32_t> ns(size_t(nt), 0u), ns_off(size_t(nt) + 1, 0u);
+  for (int64_t t = 0; t < nt; ++t) {
+    ns[size_t(t)] = ties ? uint32_t(ties->n_scalars[t]) : prog.n_consts[size_t(t)];
+    ns_off[size_t(t) + 1] = ns_off[size_t(t)] + ns[size_t(t)];
+  }
   std::vector<uint32_t> tan_off(size_t(nt) + 1, 0u), tan_par;
   if (parametric) {
     std::vector<uint32_t> used;
@@ -2771,16 +2780,45 @@ int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_gr
     }
   }
   // where tree t's gradient starts in out_grad
-  auto goff = [&](int64_t t) -> size_t { return size_t(prog.const_off[size_t(t)]) + size_t(t) * size_t(pK * pC); };
+  auto goff = [&](int64_t t) -> size_t { return size_t(ns_off[size_t(t)]) + size_t(t) * size_t(pK * pC); };
   // pre-order constants of every tree (get_scalar_constants order)
   const T* vals = static_cast<const T*>(trees->val);
   std::vector<T> consts;
   consts.reserve(size_t(prog.const_off[size_t(nt)]));
-  for (int64_t t = 0; t < nt; ++t)
-    for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i)
-      if (trees->degree[i] == 0 && trees->constant[i]) consts.push_back(vals[i]);
+  if (!ties) {
+    for (int64_t t = 0; t < nt; ++t)
+      for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i)
+        if (trees->degree[i] == 0 && trees->constant[i]) consts.push_back(vals[i]);
+  } else {
+    // the constant table per tree: scalar s at entry s (all its copies must hold one value), the frozen
+    // constants behind them in pre-order — the indices the tied compile gave the operands.  A scalar without a
+    // constant node in the tree (an unread entry of a parameter vector; a sub-expression called only inside
+    // a dropped argument) keeps the entry 0: no operand names it, so its tangent and its derivative are 0
+    consts.assign(size_t(prog.const_off[size_t(nt)]), T(0));
+    std::vector<uint8_t> seen;
+    size_t j = 0;  // constant node of the batch
+    for (int64_t t = 0; t < nt; ++t) {
+      T* tab = consts.data() + prog.const_off[size_t(t)];
+      const uint32_t n_s = ns[size_t(t)];
+      uint32_t frozen = 0;
+      seen.assign(n_s, 0);
+      for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i) {
+        if (!(trees->degree[i] == 0 && trees->constant[i])) continue;
+        const int32_t sl = ties->slot[j++];
+        if (sl < 0) {
+          tab[n_s + frozen++] = vals[i];
+        } else if (seen[size_t(sl)] && std::memcmp(&tab[sl], &vals[i], sizeof(T)) != 0) {
+          return set_error(SR_ERR_INVALID_ARG, "tree " + std::to_string(t) + ": copies of scalar " + std::to_string(sl) +
+                                                   " hold different values");
+        } else {
+          tab[sl] = vals[i];
+          seen[size_t(sl)] = 1;
+        }
+      }
+    }
+  }
   T* g = static_cast<T*>(out_grad);
-  std::fill(g, g + consts.size() + size_t(nt) * size_t(pK * pC), T(0));
+  std::fill(g, g + size_t(ns_off[size_t(nt)]) + size_t(nt) * size_t(pK * pC), T(0));
   // work items per tangent width: (tree, first constant)
   // tangent buckets: a tree runs with the narrowest width that holds its constants (1, 2, 4, 8; more
   // than 8: passes of 16), so a one-constant tree carries one tangent, not four
@@ -2790,11 +2828,15 @@ int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_gr
   for (int64_t t = 0; t < nt; ++t) {
     // (tangents: the constants and, in a parametric call, the used parameters behind them; the limit is
     //  one on constants, which live in the kernel's cval lanes)
-    const uint32_t nc = prog.n_consts[size_t(t)] + (tan_off[size_t(t) + 1] - tan_off[size_t(t)]);
+    //  (ties: a plain call's windows cover the scalars alone; a parametric one's tangent positions are table
+    //   entries, then the used parameters, and a window holding frozen constants only is left out)
+    const uint32_t ntab = prog.n_consts[size_t(t)];
+    const uint32_t nc = (parametric ? ntab : ns[size_t(t)]) + (tan_off[size_t(t) + 1] - tan_off[size_t(t)]);
     if (nc == 0 || !out_complete[t]) continue;
-    if (prog.n_consts[size_t(t)] > 128) return set_error(SR_ERR_TOO_DEEP, "more than 128 constants in one tree");
+    if (ntab > 128) return set_error(SR_ERR_TOO_DEEP, "more than 128 constants in one tree");
     const int b = nc <= 1 ? 0 : (nc <= 2 ? 1 : (nc <= 4 ? 2 : (nc <= 8 ? 3 : 4)));
     for (uint32_t k0 = 0; k0 < nc; k0 += uint32_t(kts[b])) {
+      if (k0 >= ns[size_t(t)] && k0 + uint32_t(kts[b]) <= ntab) continue;
       items[b].push_back(uint32_t(t));
       k0s[b].push_back(k0);
     }
@@ -3081,8 +3123,8 @@ int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_gr
     const int kt = kts[b];
     for (size_t i = 0; i < items[b].size(); ++i) {
       const uint32_t t = items[b][i], k0 = k0s[b][i];
-      const uint32_t nc = prog.n_consts[t];
-      for (int q = 0; q < kt && k0 + uint32_t(q) < nc; ++q)
+      const uint32_t nc = prog.n_consts[t];  // (where the parameter tangents start: the table's entries)
+      for (int q = 0; q < kt && k0 + uint32_t(q) < ns[t]; ++q)
         g[goff(t) + k0 + uint32_t(q)] = T(out[o_vals[b] + i * size_t(kt) + size_t(q)] / vden[size_t(view_of(t))]);
       if (!parametric) continue;
       // the window's parameter tangents: bin (rank, class) -> entry nc + k + K class
@@ -3091,7 +3133,7 @@ int eval_grad_impl(sr_ctx* ctx, const EvalReq& req, void* out_loss, void* out_gr
       for (uint32_t q = q0; q < q1; ++q) {
         const uint32_t k = tan_par[tan_off[t] + (k0 + q - nc)];
         for (int64_t c = 0; c < pC; ++c)
-          g[goff(t) + nc + size_t(k) + size_t(pK) * size_t(c)] =
+          g[goff(t) + ns[t] + size_t(k) + size_t(pK) * size_t(c)] =
               T(out[o_bins[b] + item_bin[b][i] + size_t(q - q0) * size_t(pC) + size_t(c)] / vden[size_t(view_of(t))]);
       }
     }
@@ -4592,6 +4634,17 @@ int sr_eval_grad_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_i
   return eval_entry(ctx, req, kEvalGrad, true, out_loss, out_grad, out_complete);
 }
 
+// Gradients with tied / frozen constants (sr_scalar_ties): per tree [n_scalars | K x C when params]; the
+// loss and flags are the untied calls'.
+int sr_eval_grad_batch_tied(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                            const sr_param_batch* params, const sr_scalar_ties* ties, const int64_t* row_idx,
+                            int64_t n_idx, int loss_kind, void* out_loss, void* out_grad, uint8_t* out_complete) {
+  if (!ties || (trees && trees->n_trees > 0 && (!ties->slot || !ties->n_scalars)))
+    return set_error(SR_ERR_INVALID_ARG, "NULL scalar ties");
+  EvalReq req{ds, opset_id, trees, params, row_idx, n_idx, nullptr, loss_kind, ties};
+  return eval_entry(ctx, req, kEvalGrad, params != nullptr, out_loss, out_grad, out_complete);
+}
+
 int sr_eval_grad_batch_views(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
                              const int32_t* tree_view, int n_views, const int64_t* view_rows, int64_t view_len,
                              int loss_kind, void* out_loss, void* out_grad, uint8_t* out_complete) {
@@ -5005,7 +5058,8 @@ int sr_finalize_losses(int dtype, int64_t n_trees, const double* sums, const uin
 static int compile_info_impl(int dtype, int n_unary, const char* const* unary_names, int n_binary,
                              const char* const* binary_names, const sr_tree_batch* trees, const SrParamNodes* pn,
                              int64_t n_rows, int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad,
-                             int32_t* out_max_depth, void* out_code, int64_t code_capacity, bool grad = false) {
+                             int32_t* out_max_depth, void* out_code, int64_t code_capacity, bool grad = false,
+                             const sr_scalar_ties* ties = nullptr) {
   if (!trees || n_unary < 0 || n_binary < 0 || (n_unary > 0 && !unary_names) || (n_binary > 0 && !binary_names))
     return set_error(SR_ERR_INVALID_ARG, "bad arguments");
   SrOpset o;
@@ -5037,13 +5091,13 @@ static int compile_info_impl(int dtype, int n_unary, const char* const* unary_na
   };
   if (dtype == SR_DTYPE_F32) {
     SrProgramBatch<float> prog;
-    int rc = sr_compile_batch<float>(*trees, o, n_rows, nfeatures, grad, &prog, &err, nullptr, pn);
+    int rc = sr_compile_batch<float>(*trees, o, n_rows, nfeatures, grad, &prog, &err, nullptr, pn, ties);
     if (rc != SR_OK) return set_error(rc, err);
     return report(prog);
   }
   if (dtype == SR_DTYPE_F64) {
     SrProgramBatch<double> prog;
-    int rc = sr_compile_batch<double>(*trees, o, n_rows, nfeatures, grad, &prog, &err, nullptr, pn);
+    int rc = sr_compile_batch<double>(*trees, o, n_rows, nfeatures, grad, &prog, &err, nullptr, pn, ties);
     if (rc != SR_OK) return set_error(rc, err);
     return report(prog);
   }
@@ -5088,6 +5142,19 @@ int sr_compile_info_grad_parametric(int dtype, int n_unary, const char* const* u
   const SrParamNodes pn{params->is_parameter, params->parameter, params->max_parameters};
   return compile_info_impl(dtype, n_unary, unary_names, n_binary, binary_names, trees, &pn, n_rows, nfeatures, out_len,
                            out_static_bad, out_max_depth, out_code, code_capacity, true);
+}
+
+int sr_compile_info_grad_tied(int dtype, int n_unary, const char* const* unary_names, int n_binary,
+                              const char* const* binary_names, const sr_tree_batch* trees,
+                              const sr_param_batch* params, const sr_scalar_ties* ties, int64_t n_rows,
+                              int64_t nfeatures, int32_t* out_len, uint8_t* out_static_bad, int32_t* out_max_depth,
+                              void* out_code, int64_t code_capacity) {
+  if (!ties) return set_error(SR_ERR_INVALID_ARG, "NULL scalar ties");
+  if (params && (params->max_parameters < 0 || params->max_parameters > 65535)) return set_error(SR_ERR_INVALID_ARG, "bad max_parameters");
+  SrParamNodes pn{};
+  if (params) pn = SrParamNodes{params->is_parameter, params->parameter, params->max_parameters};
+  return compile_info_impl(dtype, n_unary, unary_names, n_binary, binary_names, trees, params ? &pn : nullptr, n_rows,
+                           nfeatures, out_len, out_static_bad, out_max_depth, out_code, code_capacity, true, ties);
 }
 
 int sr_host_unary(int dtype, const char* name, int64_t n, const void* x, void* out) {

@@ -190,6 +190,10 @@ struct TreeCompiler {
 
   const int16_t* derived = nullptr;  // [SR_U_COUNT][nfeatures]: derived column of unary(feature), -1 none
   int max_params = 0;                // parameter leaves name p1 .. p<max_params>
+  // tied gradient programs (sr_scalar_ties): this tree's constant nodes' scalar slots (-1 frozen) and its
+  // scalar count; NULL: every constant its own pre-order slot
+  const int32_t* tie_slot = nullptr;
+  int32_t tie_ns = 0;
   // constant-operand binaries fused as PBC fields (SR_AMD_PBC=0 turns it off: A/B runs)
   const bool fuse_pbc = [] {
     static const bool on = [] {
@@ -643,6 +647,18 @@ struct TreeCompiler {
   void number_constants() {
     reset_n(const_slot, t.n, -1);
     uint32_t k = 0;
+    if (tie_slot) {
+      // a scalar's copies share its slot; frozen constants sit behind the scalars in the constant table
+      uint32_t frozen = 0;
+      for (int64_t i = 0; i < t.n; ++i) {
+        if (!(t.degree[i] == 0 && t.constant[i])) continue;
+        const int32_t s = tie_slot[k++];
+        if (s >= tie_ns) fail(SR_ERR_INVALID_ARG, "scalar slot out of range");
+        const_slot[i] = s >= 0 ? s : int32_t(uint32_t(tie_ns) + frozen++);
+      }
+      n_consts = uint32_t(tie_ns) + frozen;
+      return;
+    }
     for (int64_t i = 0; i < t.n; ++i)
       if (t.degree[i] == 0 && t.constant[i]) const_slot[i] = int32_t(k++);
     n_consts = k;
@@ -774,8 +790,12 @@ void sr_parallel_for(int n, const std::function<void(int)>& fn) {
 template <typename T>
 int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_rows, int64_t nfeatures,
                      bool with_const_index, SrProgramBatch<T>* out, std::string* err, const int16_t* derived,
-                     const SrParamNodes* pn) {
+                     const SrParamNodes* pn, const sr_scalar_ties* ties) {
   const int64_t nt = trees.n_trees;
+  if (ties && nt > 0 && (!with_const_index || !ties->slot || !ties->n_scalars)) {
+    *err = "sr_scalar_ties has NULL arrays (or is given to a program kind without constant slots)";
+    return SR_ERR_INVALID_ARG;
+  }
   if (pn && nt > 0 && (!pn->is_parameter || !pn->parameter || pn->max_parameters < 0)) {
     *err = "sr_param_batch has NULL arrays";
     return SR_ERR_INVALID_ARG;
@@ -795,6 +815,16 @@ int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_r
     int64_t nodes, ops;
   };
   std::vector<PerTree> per(size_t(nt > 0 ? nt : 0));
+  // ties: where each tree's constant nodes start in ties->slot
+  std::vector<int64_t> tie_off;
+  if (ties && nt > 0) {
+    tie_off.assign(size_t(nt) + 1, 0);
+    for (int64_t k = 0; k < nt; ++k) {
+      int64_t c = 0;
+      for (int64_t i = trees.offsets[k]; i < trees.offsets[k + 1]; ++i) c += (trees.degree[i] == 0 && trees.constant[i]) ? 1 : 0;
+      tie_off[size_t(k) + 1] = tie_off[size_t(k)] + c;
+    }
+  }
   std::vector<int> errs(size_t(nt > 0 ? nt : 0), SR_OK);
   const T* vals = static_cast<const T*>(trees.val);
   // work split: pieces of 32..256 trees, about four per persistent worker (round 5: 128 at least
@@ -833,6 +863,14 @@ int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_r
       if (pn) {
         tree.is_param = pn->is_parameter + b;
         tree.param = pn->parameter + b;
+      }
+      if (ties) {
+        tc.tie_slot = ties->slot + tie_off[size_t(k)];
+        tc.tie_ns = ties->n_scalars[k];
+        if (tc.tie_ns < 0) {
+          errs[k] = SR_ERR_INVALID_ARG;
+          continue;
+        }
       }
       tc.run(tree);
       if (tc.err != SR_OK) {
@@ -919,6 +957,8 @@ int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_r
 }
 
 template int sr_compile_batch<float>(const sr_tree_batch&, const SrOpset&, int64_t, int64_t, bool,
-                                     SrProgramBatch<float>*, std::string*, const int16_t*, const SrParamNodes*);
+                                     SrProgramBatch<float>*, std::string*, const int16_t*, const SrParamNodes*,
+                                     const sr_scalar_ties*);
 template int sr_compile_batch<double>(const sr_tree_batch&, const SrOpset&, int64_t, int64_t, bool,
-                                      SrProgramBatch<double>*, std::string*, const int16_t*, const SrParamNodes*);
+                                      SrProgramBatch<double>*, std::string*, const int16_t*, const SrParamNodes*,
+                                      const sr_scalar_ties*);

@@ -76,6 +76,10 @@ uint32_t sr_instruction_cost(uint32_t opcode);
 // LOAD_PARAM / a P binary operand (sr_ops.h).  With with_const_index (gradient programs) the program is
 // that of the tree with p_k replaced by feature nfeatures + k, apart from those opcodes and the operand
 // index (k - 1): the same length, depth and constant slots (make param-grad-check).
+// ties: optional (gradient programs only) scalar slots of a batch whose constants are tied / frozen
+// (include/sr_amd.h sr_scalar_ties): a constant operand's index is its scalar slot, a frozen constant's
+// n_scalars + its rank among the tree's frozen constants, and n_consts counts the table entries (scalars +
+// frozen).  Without ties the programs are what they were.
 struct SrParamNodes {
   const uint8_t* is_parameter;
   const uint16_t* parameter;  // 1-based, <= max_parameters
@@ -84,4 +88,5 @@ struct SrParamNodes {
 template <typename T>
 int sr_compile_batch(const sr_tree_batch& trees, const SrOpset& ops, int64_t n_rows, int64_t nfeatures,
                      bool with_const_index, SrProgramBatch<T>* out, std::string* err,
-                     const int16_t* derived = nullptr, const SrParamNodes* pn = nullptr);
+                     const int16_t* derived = nullptr, const SrParamNodes* pn = nullptr,
+                     const sr_scalar_ties* ties = nullptr);

@@ -48,6 +48,20 @@ inline std::vector<double> axpy(const std::vector<double>& x, double a, const st
   return o;
 }
 
+// Tied constants (sr_scalar_ties): the optimiser iterates on a tree's scalar vector x, and before every loss
+// or gradient call each scalar is written to ALL its copies among the tree's n nodes — slot[j] names the
+// scalar of the tree's j-th constant node (pre-order), -1 a frozen constant, whose value is never touched.
+template <typename T>
+inline void spread_scalars(const uint8_t* degree, const uint8_t* constant, int64_t n, const int32_t* slot,
+                           const std::vector<double>& x, T* val) {
+  int64_t j = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!(degree[i] == 0 && constant[i])) continue;
+    const int32_t s = slot[j++];
+    if (s >= 0) val[i] = T(x[size_t(s)]);
+  }
+}
+
 // one BackTracking interpolation step (quadratic on the first iteration, cubic after)
 inline double backtrack_step(double phi0, double dphi0, double a1, double a2, double phix0, double phix1, int it) {
   double a_tmp;

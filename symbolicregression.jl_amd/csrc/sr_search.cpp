@@ -1470,16 +1470,21 @@ int optimize_common(Scorer<T>& sc, const sr_tree_batch* trees, const int64_t* ro
   return SR_OK;
 }
 
-// The BFGS objective over a batch of ParametricExpression trees, beside TreeObjective: item k = tree k with
-// x = [its constants in pre-order; vec(parameters)] (sr_param_pack.h) rounded to T, one batched parametric
-// device call per evaluation round.
+// The BFGS objective over a batch whose optimised vector is packed (sr_param_pack.h), beside TreeObjective:
+// item k = tree k with x = [its scalars; vec(parameters) when the batch is parametric] rounded to T, one
+// batched device call per evaluation round.  Without ties (sr_optimize_constants_batch_parametric) the
+// scalars are the tree's constants in pre-order; with ties (sr_scalar_ties) every scalar is written to all
+// its copies before each call (srco::spread_scalars) and frozen constants keep their values.
 template <typename T>
-struct ParamObjective : SrObjective {
+struct PackedObjective : SrObjective {
   sr_ctx* ctx = nullptr;
   const sr_dataset* ds = nullptr;
   int opset_id = 0, loss_code = 0;
   const sr_tree_batch* trees = nullptr;
-  const sr_param_batch* params = nullptr;
+  const sr_param_batch* params = nullptr;  // NULL: plain trees (tied calls only)
+  const sr_scalar_ties* ties = nullptr;    // NULL: every constant its own scalar
+  std::vector<int64_t> tie_off;            // [n_trees + 1] into ties->slot
+  std::vector<size_t> n_scalars;           // per tree
   const int64_t* row_idx = nullptr;
   int64_t n_idx = 0;
   std::vector<int64_t> f_calls;
@@ -1488,27 +1493,39 @@ struct ParamObjective : SrObjective {
   std::vector<uint8_t> degree, op, constant, isp;
   std::vector<uint16_t> feature, par;
   std::vector<T> val, mats;
-  size_t kc() const { return size_t(params->max_parameters) * size_t(params->n_classes); }
-  void build(const std::vector<int>& items, const std::vector<std::vector<double>>& xs, sr_tree_batch* tb, sr_param_batch* pb) {
+  std::vector<int32_t> slot, nsc;
+  size_t kc() const { return params ? size_t(params->max_parameters) * size_t(params->n_classes) : 0; }
+  void build(const std::vector<int>& items, const std::vector<std::vector<double>>& xs, sr_tree_batch* tb, sr_param_batch* pb,
+             sr_scalar_ties* st) {
     offs.assign(1, 0);
     degree.clear(), op.clear(), constant.clear(), isp.clear(), feature.clear(), par.clear(), val.clear();
+    slot.clear(), nsc.clear();
     mats.assign(items.size() * kc(), T(0));
     const T* vals = static_cast<const T*>(trees->val);
     for (size_t j = 0; j < items.size(); ++j) {
       const int64_t t = items[j];
-      size_t q = 0;
-      for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i) {
-        degree.push_back(trees->degree[i]);
-        op.push_back(trees->op[i]);
-        feature.push_back(trees->feature[i]);
-        constant.push_back(trees->constant[i]);
-        isp.push_back(params->is_parameter[i]);
-        par.push_back(params->parameter[i]);
-        const bool c = trees->degree[i] == 0 && trees->constant[i];
-        val.push_back(c ? T(xs[j][q]) : vals[i]);
-        q += c ? 1 : 0;
+      const int64_t b = trees->offsets[t], e = trees->offsets[t + 1];
+      const size_t at = val.size();
+      degree.insert(degree.end(), trees->degree + b, trees->degree + e);
+      op.insert(op.end(), trees->op + b, trees->op + e);
+      feature.insert(feature.end(), trees->feature + b, trees->feature + e);
+      constant.insert(constant.end(), trees->constant + b, trees->constant + e);
+      if (params) {
+        isp.insert(isp.end(), params->is_parameter + b, params->is_parameter + e);
+        par.insert(par.end(), params->parameter + b, params->parameter + e);
+      }
+      val.insert(val.end(), vals + b, vals + e);
+      if (ties) {
+        srco::spread_scalars<T>(trees->degree + b, trees->constant + b, e - b, ties->slot + tie_off[size_t(t)], xs[j], val.data() + at);
+        slot.insert(slot.end(), ties->slot + tie_off[size_t(t)], ties->slot + tie_off[size_t(t) + 1]);
+        nsc.push_back(ties->n_scalars[t]);
+      } else {
+        size_t q = 0;
+        for (int64_t i = b; i < e; ++i)
+          if (trees->degree[i] == 0 && trees->constant[i]) val[at + size_t(i - b)] = T(xs[j][q++]);
       }
       offs.push_back(int64_t(degree.size()));
+      const size_t q = n_scalars[size_t(t)];
       for (size_t m = 0; m < kc(); ++m) mats[j * kc() + m] = T(xs[j][q + m]);
     }
     *tb = sr_tree_batch{};
@@ -1519,17 +1536,20 @@ struct ParamObjective : SrObjective {
     tb->feature = feature.data();
     tb->constant = constant.data();
     tb->val = val.data();
-    *pb = sr_param_batch{isp.data(), par.data(), params->max_parameters, params->n_classes, mats.data()};
+    if (params) *pb = sr_param_batch{isp.data(), par.data(), params->max_parameters, params->n_classes, mats.data()};
+    *st = sr_scalar_ties{slot.data(), nsc.data()};
   }
   int f(const std::vector<int>& items, const std::vector<std::vector<double>>& xs, std::vector<double>* out) override {
     sr_tree_batch tb;
     sr_param_batch pb;
-    build(items, xs, &tb, &pb);
+    sr_scalar_ties st;
+    build(items, xs, &tb, &pb, &st);
     if (counting)
       for (int k : items) ++f_calls[size_t(k)];
     std::vector<T> loss(items.size());
     std::vector<uint8_t> comp(items.size());
-    const int rc = sr_eval_loss_batch_parametric(ctx, ds, opset_id, &tb, &pb, row_idx, n_idx, loss_code, loss.data(), comp.data());
+    const int rc = params ? sr_eval_loss_batch_parametric(ctx, ds, opset_id, &tb, &pb, row_idx, n_idx, loss_code, loss.data(), comp.data())
+                          : sr_eval_loss_batch(ctx, ds, opset_id, &tb, row_idx, n_idx, loss_code, loss.data(), comp.data());
     if (rc) return rc;
     out->resize(items.size());
     for (size_t j = 0; j < items.size(); ++j) (*out)[j] = comp[j] ? double(loss[j]) : INFINITY;
@@ -1539,7 +1559,8 @@ struct ParamObjective : SrObjective {
          std::vector<std::vector<double>>* grads) override {
     sr_tree_batch tb;
     sr_param_batch pb;
-    build(items, xs, &tb, &pb);
+    sr_scalar_ties st;
+    build(items, xs, &tb, &pb, &st);
     size_t n = 0;
     for (size_t j = 0; j < items.size(); ++j) {
       if (counting) ++f_calls[size_t(items[j])];
@@ -1547,8 +1568,10 @@ struct ParamObjective : SrObjective {
     }
     std::vector<T> loss(items.size()), g(n + 1, T(0));
     std::vector<uint8_t> comp(items.size());
-    const int rc = sr_eval_grad_batch_parametric(ctx, ds, opset_id, &tb, &pb, row_idx, n_idx, loss_code, loss.data(),
-                                                 g.data(), comp.data());
+    const int rc = ties ? sr_eval_grad_batch_tied(ctx, ds, opset_id, &tb, params ? &pb : nullptr, &st, row_idx, n_idx, loss_code,
+                                                  loss.data(), g.data(), comp.data())
+                        : sr_eval_grad_batch_parametric(ctx, ds, opset_id, &tb, &pb, row_idx, n_idx, loss_code, loss.data(),
+                                                        g.data(), comp.data());
     if (rc) return rc;
     out->resize(items.size());
     grads->resize(items.size());
@@ -1563,34 +1586,57 @@ struct ParamObjective : SrObjective {
   }
 };
 
+// sr_optimize_constants_batch_parametric (ties NULL) and sr_optimize_constants_batch_tied (params may be NULL):
+// x0 = [scalars; vec(P)] per tree, the restarts x0 .* (1 + eps / 2) over the whole vector, drawn per tree then
+// per restart as the plain optimiser draws them.  A tied scalar starts from its copies' common value (copies
+// that differ are refused, as sr_eval_grad_batch_tied refuses them); a scalar without a constant node starts
+// from 0 and stays there (its derivative is 0): the caller keeps its own value for it.
 template <typename T>
-int optimize_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
-                        const sr_param_batch* params, const int64_t* row_idx, int64_t n_idx, int loss_kind, int iterations,
-                        int64_t f_calls_limit, int nrestarts, uint64_t seed, void* out_consts, void* out_params,
-                        void* out_loss, uint8_t* out_improved, int64_t* out_f_calls) {
+int optimize_packed(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees, const sr_param_batch* params,
+                    const sr_scalar_ties* ties, const int64_t* row_idx, int64_t n_idx, int loss_kind, int iterations,
+                    int64_t f_calls_limit, int nrestarts, uint64_t seed, void* out_scalars, void* out_params, void* out_loss,
+                    uint8_t* out_improved, int64_t* out_f_calls) {
   const int64_t nt = trees->n_trees;
-  ParamObjective<T> obj;
+  PackedObjective<T> obj;
   obj.ctx = ctx;
   obj.ds = ds;
   obj.opset_id = opset_id;
   obj.loss_code = loss_kind;
   obj.trees = trees;
   obj.params = params;
+  obj.ties = ties;
   obj.row_idx = row_idx && n_idx > 0 ? row_idx : nullptr;
   obj.n_idx = row_idx && n_idx > 0 ? n_idx : 0;
   obj.f_calls.assign(size_t(nt), 0);
+  obj.n_scalars.assign(size_t(nt), 0);
+  obj.tie_off.assign(size_t(nt) + 1, 0);
   const size_t kc = obj.kc();
   const T* vals = static_cast<const T*>(trees->val);
-  const T* pm = static_cast<const T*>(params->parameters);
-  // x0 = [constants; vec(P)] per tree, and the restarts x0 .* (1 + eps / 2) over the whole vector, drawn
-  // per tree then per restart as the plain optimiser draws them
+  const T* pm = params ? static_cast<const T*>(params->parameters) : nullptr;
   std::vector<std::vector<double>> x0(static_cast<size_t>(nt));
-  std::vector<size_t> ncs(static_cast<size_t>(nt));
   for (int64_t t = 0; t < nt; ++t) {
     std::vector<T> c;
-    for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i)
-      if (trees->degree[i] == 0 && trees->constant[i]) c.push_back(vals[i]);
-    ncs[size_t(t)] = c.size();
+    if (!ties) {
+      for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i)
+        if (trees->degree[i] == 0 && trees->constant[i]) c.push_back(vals[i]);
+    } else {
+      if (ties->n_scalars[t] < 0) return sr_set_error(SR_ERR_INVALID_ARG, "negative scalar count");
+      c.assign(size_t(ties->n_scalars[t]), T(0));
+      std::vector<uint8_t> seen(c.size(), 0);
+      int64_t j = obj.tie_off[size_t(t)];
+      for (int64_t i = trees->offsets[t]; i < trees->offsets[t + 1]; ++i) {
+        if (!(trees->degree[i] == 0 && trees->constant[i])) continue;
+        const int32_t sl = ties->slot[j++];
+        if (sl >= int32_t(c.size())) return sr_set_error(SR_ERR_INVALID_ARG, "scalar slot out of range");
+        if (sl < 0) continue;
+        if (seen[size_t(sl)] && memcmp(&c[size_t(sl)], &vals[i], sizeof(T)) != 0)
+          return sr_set_error(SR_ERR_INVALID_ARG, "copies of one scalar hold different values");
+        c[size_t(sl)] = vals[i];
+        seen[size_t(sl)] = 1;
+      }
+      obj.tie_off[size_t(t) + 1] = j;
+    }
+    obj.n_scalars[size_t(t)] = c.size();
     srpp::pack<T>(c.data(), c.size(), kc ? pm + size_t(t) * kc : nullptr, kc, &x0[size_t(t)]);
   }
   SrRng rng;
@@ -1622,8 +1668,9 @@ int optimize_parametric(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const s
   for (int64_t t = 0; t < nt; ++t) {
     const bool imp = jb < better.size() && better[jb] == int(t);
     const std::vector<double>& x = imp ? bx[size_t(t)] : x0[size_t(t)];
-    srpp::unpack<T>(x, ncs[size_t(t)], static_cast<T*>(out_consts) + at, static_cast<T*>(out_params) + size_t(t) * kc, kc);
-    at += ncs[size_t(t)];
+    const size_t n_s = obj.n_scalars[size_t(t)];
+    srpp::unpack<T>(x, n_s, static_cast<T*>(out_scalars) + at, kc ? static_cast<T*>(out_params) + size_t(t) * kc : nullptr, kc);
+    at += n_s;
     static_cast<T*>(out_loss)[t] = imp ? T(lb[jb]) : T(base[size_t(t)]);
     out_improved[t] = imp ? 1 : 0;
     out_f_calls[t] = obj.f_calls[size_t(t)];
@@ -1934,10 +1981,39 @@ int sr_optimize_constants_batch_parametric(sr_ctx* ctx, const sr_dataset* ds, in
   const int rc = sr_dataset_info(ds, &dt, &nf, &n);
   if (rc) return rc;
   if (dt == SR_DTYPE_F32)
-    return optimize_parametric<float>(ctx, ds, opset_id, trees, params, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
+    return optimize_packed<float>(ctx, ds, opset_id, trees, params, nullptr, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
                                       nrestarts, seed, out_consts, out_params, out_loss, out_improved, out_f_calls);
-  return optimize_parametric<double>(ctx, ds, opset_id, trees, params, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
+  return optimize_packed<double>(ctx, ds, opset_id, trees, params, nullptr, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
                                      nrestarts, seed, out_consts, out_params, out_loss, out_improved, out_f_calls);
+}
+
+int sr_optimize_constants_batch_tied(sr_ctx* ctx, const sr_dataset* ds, int opset_id, const sr_tree_batch* trees,
+                                     const sr_param_batch* params, const sr_scalar_ties* ties, const int64_t* row_idx,
+                                     int64_t n_idx, int loss_kind, int iterations, int64_t f_calls_limit,
+                                     int nrestarts, uint64_t seed, void* out_scalars, void* out_params, void* out_loss,
+                                     uint8_t* out_improved, int64_t* out_f_calls) {
+  if (!ctx || !ds || !trees || !ties) return sr_set_error(SR_ERR_INVALID_ARG, "NULL context, dataset, trees or ties");
+  if (iterations < 0 || nrestarts < 0 || f_calls_limit < 0)
+    return sr_set_error(SR_ERR_INVALID_ARG, "negative iterations / f_calls_limit / restarts");
+  const int64_t nt = trees->n_trees;
+  if (nt < 0) return sr_set_error(SR_ERR_INVALID_ARG, "negative tree count");
+  if (nt == 0) return SR_OK;
+  if (params && (params->max_parameters < 0 || params->max_parameters > 65535 || params->n_classes < 1))
+    return sr_set_error(SR_ERR_INVALID_ARG, "bad max_parameters / n_classes");
+  if (!trees->offsets || !trees->degree || !trees->op || !trees->feature || !trees->constant || !trees->val ||
+      !ties->slot || !ties->n_scalars ||
+      (params && (!params->is_parameter || !params->parameter || (params->max_parameters > 0 && (!params->parameters || !out_params)))) ||
+      !out_scalars || !out_loss || !out_improved || !out_f_calls)
+    return sr_set_error(SR_ERR_INVALID_ARG, "NULL arrays");
+  int dt = 0;
+  int64_t nf = 0, n = 0;
+  const int rc = sr_dataset_info(ds, &dt, &nf, &n);
+  if (rc) return rc;
+  if (dt == SR_DTYPE_F32)
+    return optimize_packed<float>(ctx, ds, opset_id, trees, params, ties, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
+                                nrestarts, seed, out_scalars, out_params, out_loss, out_improved, out_f_calls);
+  return optimize_packed<double>(ctx, ds, opset_id, trees, params, ties, row_idx, n_idx, loss_kind, iterations, f_calls_limit,
+                               nrestarts, seed, out_scalars, out_params, out_loss, out_improved, out_f_calls);
 }
 
 int sr_optimize_constants_callbacks(int dtype, const sr_tree_batch* trees, const int64_t* row_idx, int64_t n_idx,

@@ -395,6 +395,77 @@ function eval_grad_batch(trees::AbstractVector, dataset::Dataset{T,L}, options::
     return L.(losses), grads[1:end-1], complete .== 0x01
 end
 
+# ---------------------------------------------------------------- TemplateExpression candidates (DESIGN.md §16)
+struct SrScalarTies
+    slot::Ptr{Int32}       # per constant node of the batch, pre-order: scalar index within its tree, -1 frozen
+    n_scalars::Ptr{Int32}  # per tree
+end
+
+"""The composed tree of a parameter-free `TemplateExpression` (`DE.get_tree`, src/TemplateExpression.jl:474-498)
+and, per constant node of it in pre-order, the index of its scalar in `get_scalar_constants(ex)` or -1 for a
+literal of the structure.  The provenance of the copies is found by value-tagging: in a copy of the template
+scalar i is replaced by the tag `-i`, the copy is composed, and each constant of the composed tree is read
+back: a tag names its scalar, anything else is a literal.  The values come from the untagged composition,
+which has the same shape.  A literal of the structure that equals a tag would be taken for a scalar: it is
+the one constant that holds a tag's value in BOTH compositions although its scalar's own value is another,
+and that is an error here (pass another `tag`)."""
+function template_ties(ex::TemplateExpression; tag=i -> -Float64(i))
+    x, refs = get_scalar_constants(ex)
+    tagged = copy(ex)
+    set_scalar_constants!(tagged, eltype(x).(tag.(eachindex(x))), refs)
+    tree, shape = get_tree(ex), get_tree(tagged)
+    tags = Dict(eltype(x)(tag(i)) => Int32(i - 1) for i in eachindex(x))
+    slot = Int32[]
+    foreach(shape) do node
+        node.degree == 0 && node.constant && push!(slot, get(tags, node.val, Int32(-1)))
+    end
+    vals = eltype(x)[]
+    foreach(tree) do node
+        node.degree == 0 && node.constant && push!(vals, node.val)
+    end
+    length(vals) == length(slot) || error("template_ties: the tagged composition has another shape")
+    for (v, s) in zip(vals, slot)
+        # a scalar's copy holds x[s + 1] in the untagged tree; a tag-valued constant that does not is a literal
+        s >= 0 && !isequal(v, x[s + 1]) && error("template_ties: a literal of the structure equals the tag of scalar $(s + 1); pass another `tag`")
+    end
+    return tree, slot, Int32(length(x))
+end
+
+"""Batched objective + gradient of parameter-free templates with tied constants: `sr_eval_grad_batch_tied` on the
+composed trees.  Gradients come back per template in `get_scalar_constants` order (sub-expression constants in
+key order).  Arguments a callee drops (`f(x1, x2 / x3)` with `f = #1`) are not in `get_tree`: the caller adds
+their composed trees to `trees` as guards (slot -1 throughout, `n_scalars = 0`) and ANDs the flags, as
+sr_amd/template.py does; templates with parameters are composed there too (`get_tree` raises for them)."""
+function eval_grad_batch_templates(exs::AbstractVector{<:TemplateExpression}, dataset::Dataset{T,L},
+                                   options::AbstractOptions, operators) where {T,L}
+    ctx = context()
+    oid = opset_id(ctx, operators)  # options.operators with the structure-only operators appended
+    lk = loss_kind(options)
+    (oid === nothing || lk === nothing) && return nothing
+    composed = map(template_ties, exs)
+    f = flatten([c[1] for c in composed], T)
+    slot = reduce(vcat, [c[2] for c in composed]; init=Int32[])
+    ns = Int32[c[3] for c in composed]
+    losses = Vector{T}(undef, length(exs))
+    complete = Vector{UInt8}(undef, length(exs))
+    grads = zeros(T, sum(ns) + 1)
+    dsh = device_dataset(ctx, dataset)
+    GC.@preserve f slot ns losses grads complete begin
+        b = SrTreeBatch(length(exs), pointer(f.offsets), pointer(f.degree), pointer(f.op),
+                        pointer(f.feature), pointer(f.constant), Ptr{Cvoid}(pointer(f.val)))
+        ties = SrScalarTies(pointer(slot), pointer(ns))
+        rc = ccall((:sr_eval_grad_batch_tied, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{SrTreeBatch}, Ptr{Cvoid}, Ref{SrScalarTies}, Ptr{Int64}, Int64, Cint,
+                    Ptr{T}, Ptr{T}, Ptr{UInt8}),
+                   ctx.handle, dsh, oid, b, C_NULL, ties, C_NULL, 0, lk, losses, grads, complete)
+        rc == SR_ERR_UNSUPPORTED_OP && return nothing
+        check(rc)
+    end
+    return L.(losses), grads[1:end-1], complete .== 0x01
+end
+# (sr_optimize_constants_batch_tied takes the same batch and ties and returns the scalars per template:
+#  set_scalar_constants!(ex, scalars, refs) writes them back, structure untouched.)
+
 """`eval_grad_tree_array(tree, X, options; variable)` on the device
 (src/InterfaceDynamicExpressions.jl:153-165): `(evaluation, gradient, complete)`, or `nothing` when the
 device cannot take the tree.  The library writes `[n_grad][n]` with rows fastest; Julia's `dx` is

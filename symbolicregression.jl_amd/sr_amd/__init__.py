@@ -16,7 +16,7 @@ from .diff import (
     eval_grad_tree_array,
     eval_grad_tree_array_batch,
 )
-from .loss import (
+from .loss import (  # noqa: I001
     compute_complexity,
     eval_cost,
     eval_cost_batch,
@@ -40,14 +40,22 @@ from .node import (
     apply_unary,
     extend_operators,
     flatten_trees,
-    get_scalar_constants,
     parse_expression,
-    set_scalar_constants,
-    string_tree,
 )
 from .operators import OperatorEnum
 from .options import LossExpression, Options, ParametricExpressionSpec
 from .search import HallOfFame, PopMember, SearchOptions, equation_search
+from .template import (  # (the accessors take a plain tree as before, and a TemplateExpression)
+    ComposedTemplate,
+    TemplateExpression,
+    TemplateExpressionSpec,
+    TemplateStructure,
+    compose,
+    get_scalar_constants,
+    get_tree,
+    set_scalar_constants,
+    string_tree,
+)
 
 __all__ = [
     "Options", "OperatorEnum", "Dataset", "SubDataset", "batch", "Node", "TreeBatch", "flatten_trees",
@@ -59,4 +67,5 @@ __all__ = [
     "gen_random_population", "gen_random_batch", "make_random_leaf", "get_context", "device_available", "DeviceContext",
     "SRError", "UnsupportedOperatorError", "optimize_constants_batch", "equation_search", "SearchOptions",
     "PopMember", "HallOfFame", "ParametricExpression", "ParametricExpressionSpec",
+    "TemplateStructure", "TemplateExpression", "TemplateExpressionSpec", "ComposedTemplate", "compose", "get_tree",
 ]

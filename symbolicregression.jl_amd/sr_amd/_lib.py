@@ -108,6 +108,9 @@ EXPORTED_SYMBOLS = (
     "sr_compile_info_grad_parametric",
     "sr_eval_grad_tree_array",
     "sr_eval_diff_tree_array",
+    "sr_eval_grad_batch_tied",
+    "sr_compile_info_grad_tied",
+    "sr_optimize_constants_batch_tied",
 )
 
 # mutation kinds in sr_search_options.mutation_weights order (SR_MUT_*)
@@ -148,6 +151,13 @@ class SrParamBatch(ctypes.Structure):
         ("max_parameters", ctypes.c_int32),
         ("n_classes", ctypes.c_int32),
         ("parameters", c_void_p),
+    ]
+
+
+class SrScalarTies(ctypes.Structure):
+    _fields_ = [
+        ("slot", POINTER(ctypes.c_int32)),
+        ("n_scalars", POINTER(ctypes.c_int32)),
     ]
 
 
@@ -310,6 +320,20 @@ def _load():
             c_int,
             [c_int, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), POINTER(SrParamBatch),
              c_int64, c_int64, P, P, POINTER(c_int), P, c_int64],
+        ),
+        "sr_eval_grad_batch_tied": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), POINTER(SrScalarTies), P, c_int64, c_int, P, P, P],
+        ),
+        "sr_compile_info_grad_tied": (
+            c_int,
+            [c_int, c_int, POINTER(c_char_p), c_int, POINTER(c_char_p), POINTER(SrTreeBatch), POINTER(SrParamBatch),
+             POINTER(SrScalarTies), c_int64, c_int64, P, P, POINTER(c_int), P, c_int64],
+        ),
+        "sr_optimize_constants_batch_tied": (
+            c_int,
+            [P, P, c_int, POINTER(SrTreeBatch), POINTER(SrParamBatch), POINTER(SrScalarTies), P, c_int64, c_int, c_int,
+             c_int64, c_int, ctypes.c_uint64, P, P, P, P, P],
         ),
         "sr_host_unary": (c_int, [c_int, c_char_p, c_int64, P, P]),
         "sr_host_elem_loss": (c_int, [c_int, c_int, c_double, c_int64, P, P, P, P]),

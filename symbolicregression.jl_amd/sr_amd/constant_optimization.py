@@ -47,8 +47,12 @@ def optimize_constants_batch(trees, dataset, options, rng=None, *, iterations=No
     and parameters (``sr_optimize_constants_batch_parametric``).  A plain batch takes
     ``sr_optimize_constants_batch`` as before.
     """
+    from . import template as _template
     from .loss import _as_batch
 
+    if _template.is_template_batch(trees):  # templates in, templates out: the scalar vector with its ties (DESIGN.md §16)
+        return _template.optimize_constants_batch(trees, dataset, options, rng, iterations=iterations,
+                                                  nrestarts=nrestarts, ctx=ctx, f_calls_limit=f_calls_limit)
     if not device_optimizer_supported(options):
         raise NotImplementedError(f"optimizer_algorithm={options.optimizer_algorithm!r} runs on the reference's CPU "
                                   "optimize_constants; the device optimiser is BFGS + BackTracking")

@@ -45,6 +45,9 @@ def _refuse_parametric(trees):
 
 
 def _prepare(trees, dataset):
+    from .template import refuse
+
+    refuse(trees, "the per-row derivative calls (eval_grad_tree_array / eval_diff_tree_array)")
     _refuse_parametric(trees)
     if not isinstance(dataset, (Dataset, SubDataset)):
         raise TypeError("dataset must be a Dataset or a SubDataset")

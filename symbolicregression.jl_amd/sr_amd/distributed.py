@@ -33,6 +33,7 @@ import numpy as np
 
 from . import _lib
 from .device import get_context, peek_context
+from . import template as _template
 from .loss import _as_batch
 
 
@@ -56,6 +57,7 @@ N_PACKED = 5  # rows of the packed partials: Σ loss, NONFINITE, BIG, STATIC, EL
 
 def gpu_partials_packed(tb, shard, options, n_total, ctx=None):
     """This rank's packed partials [5, n_trees] f64 on its row shard (GPU), on the host."""
+    _template.refuse(tb, "the sharded and partials calls")
     ctx = ctx or get_context()
     nt = tb.n_trees
     s = tb.to_struct()
@@ -281,6 +283,7 @@ def eval_loss_sharded(trees, shard, options, n_total=None, *, denom=None, group=
     import torch.distributed as dist
 
     full = shard.full
+    _template.refuse(trees, "the sharded and partials calls")
     tb = _as_batch(trees, full.dtype)
     ctx = peek_context()
     if partials_fn is None and exact_fn is None and getattr(ctx, "has_comm", False):
@@ -382,6 +385,7 @@ def eval_loss_tree_sharded(trees, dataset, options, *, group=None, score_fn=None
     import torch.distributed as dist
 
     full = getattr(dataset, "full", dataset)
+    _template.refuse(trees, "the sharded and partials calls")
     tb = _as_batch(trees, full.dtype)
     ctx = peek_context()
     if score_fn is None and getattr(ctx, "has_comm", False):

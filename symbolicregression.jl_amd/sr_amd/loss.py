@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib
 from .dataset import Dataset, SubDataset
 from .device import get_context
+from . import template as _template
 from .node import Node, ParametricExpression, TreeBatch, flatten_trees
 
 
@@ -49,6 +50,8 @@ def eval_loss_batch(trees, dataset, options, *, ctx=None):
     """
     if options.loss_function is not None or options.loss_function_expression is not None:
         raise NotImplementedError("custom objectives are evaluated by the reference CPU path")
+    if _template.is_template_batch(trees):  # composed on the host, guards scored in the same call
+        return _template.eval_loss_batch(trees, dataset, options, ctx=ctx)
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
@@ -93,6 +96,7 @@ def _views(tree_view, view_rows, nt):
 def eval_loss_batch_views(trees, dataset, options, tree_view, view_rows, *, ctx=None):
     """``eval_loss_batch`` with tree t on the rows ``view_rows[tree_view[t]]`` of ``dataset`` (a Dataset):
     every island's trees on its own minibatch (src/SingleIteration.jl:40) in ONE device call."""
+    _template.refuse(trees, "eval_loss_batch_views")
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
@@ -116,6 +120,7 @@ def eval_loss_batch_views(trees, dataset, options, tree_view, view_rows, *, ctx=
 
 def eval_grad_batch_views(trees, dataset, options, tree_view, view_rows, *, ctx=None):
     """``eval_grad_batch`` over several row views in one call (as ``eval_loss_batch_views``)."""
+    _template.refuse(trees, "eval_grad_batch_views")
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
@@ -153,6 +158,8 @@ def eval_grad_batch(trees, dataset, options, *, ctx=None):
     """
     if options.loss_function is not None or options.loss_function_expression is not None:
         raise NotImplementedError("custom objectives are evaluated by the reference CPU path")
+    if _template.is_template_batch(trees):  # gradients in get_scalar_constants(::TemplateExpression) order, concatenated
+        return _template.eval_grad_batch(trees, dataset, options, ctx=ctx)
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
@@ -189,6 +196,8 @@ def eval_grad_batch(trees, dataset, options, *, ctx=None):
 
 def eval_tree_array_batch(trees, dataset, options, *, ctx=None):
     """Predictions of every tree: (out[n_trees, n_rows], complete[n_trees])."""
+    if _template.is_template_batch(trees):
+        return _template.eval_tree_array_batch(trees, dataset, options, ctx=ctx)
     ctx = ctx or get_context()
     full = dataset.full
     tb = _as_batch(trees, full.dtype)
@@ -267,6 +276,8 @@ def eval_loss(tree, dataset, options, *, regularization: bool = True, idx=None):
 def compute_complexity(tree, options=None) -> int:
     """Default complexity = number of nodes (src/Complexity.jl:29-41)."""
     t = tree
+    if isinstance(getattr(t, "tree", t), _template.TemplateExpression):  # the SUM of the sub-expressions'
+        return _template.compute_complexity(getattr(t, "tree", t), options)
     while not isinstance(t, Node) and hasattr(t, "tree"):  # PopMember -> (ParametricExpression ->) Node
         t = t.tree
     return t.count_nodes()
@@ -284,7 +295,7 @@ def loss_to_cost(loss, use_baseline: bool, baseline, member, options, complexity
 
 def eval_cost(dataset, member, options, *, complexity=None):
     """``eval_cost`` (src/LossFunctions.jl:193-209) -> (cost, loss)."""
-    tree = member if isinstance(member, ParametricExpression) else getattr(member, "tree", member)
+    tree = member if isinstance(member, (ParametricExpression, _template.TemplateExpression)) else getattr(member, "tree", member)
     result_loss = eval_loss(tree, dataset, options)
     cost = loss_to_cost(result_loss, dataset.use_baseline, dataset.baseline_loss, member, options, complexity)
     return cost, result_loss
@@ -292,7 +303,8 @@ def eval_cost(dataset, member, options, *, complexity=None):
 
 def eval_cost_batch(members: Sequence, dataset, options, *, complexities=None):
     """Batched ``eval_cost`` for a population: one device launch for all members."""
-    trees = [m if isinstance(m, ParametricExpression) else getattr(m, "tree", m) for m in members]
+    trees = [m if isinstance(m, (ParametricExpression, _template.TemplateExpression)) else getattr(m, "tree", m)
+             for m in members]
     losses, _ = eval_loss_batch(trees, dataset, options)
     if complexities is None:
         complexities = [compute_complexity(t) for t in trees]

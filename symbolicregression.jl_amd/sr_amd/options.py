@@ -244,10 +244,14 @@ class Options:
         self.device = "mi355x"
         self.deterministic = deterministic
         self.seed = seed
-        # None (plain Expression{T,Node{T,2}}) or a ParametricExpressionSpec; the scoring calls take either
+        # None (plain Expression{T,Node{T,2}}), a ParametricExpressionSpec or a TemplateExpressionSpec; the scoring calls take either
         # kind of tree whatever the spec says, the spec bounds a parametric tree's parameter indices
         if expression_spec is not None and not isinstance(expression_spec, ParametricExpressionSpec):
-            raise ValueError("expression_spec: only ParametricExpressionSpec is supported by the device path")
+            from .template import TemplateExpressionSpec  # (imports this module's neighbours: resolved here)
+
+            if not isinstance(expression_spec, TemplateExpressionSpec):
+                raise ValueError("expression_spec: only ParametricExpressionSpec and TemplateExpressionSpec are "
+                                 "supported by the device path")
         self.expression_spec = expression_spec
 
     @property

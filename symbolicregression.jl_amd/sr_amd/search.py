@@ -353,6 +353,11 @@ def equation_search(X=None, y=None, *, niterations=10, options, weights=None, se
     of N — it advances only its own islands i % N == r and runs the head over all of them; the other
     ranks' islands are imported every iteration as they were initialised (helper engines started before
     the timed loop): the per-rank work of an N-rank search without the all-gather itself."""
+    from .template import SECTION, TemplateExpressionSpec
+
+    if isinstance(getattr(options, "expression_spec", None), TemplateExpressionSpec):
+        raise NotImplementedError("the native search engine does not evolve TemplateExpression candidates (no template "
+                                  f"mutations): score them with the batched calls ({SECTION})")
     so = search_options or SearchOptions()
     comm = _torch_comm() if distributed else None
     rank, world, allgather = comm if comm else (0, 1, None)
